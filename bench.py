@@ -15,10 +15,14 @@ feasible-node count and the per-ask bin-pack decision. Tables are resident in HB
           plain ncclAllGather of the P-row bitmaps, which `--raw-gather` selects).
           `--weak` keeps round 1's weak-scaling variant (50 000 nodes PER GPU, decision exchange only).
 
-Prints ONE JSON line (rank 0): `value` = whole-job evals/s of the timed steps; `roofline` describes the kernel with the
-largest share of a step (HIP events on the launch stream) and the whole step; `variants` re-times the two other ask
-populations of SURVEY.md §8d (every ask its own template; adversarial distinct request vectors); `end_to_end` is one cold
-pass including encode + upload + class build; `cpu_baseline` is the oracle on the host cores.
+Prints ONE JSON line (rank 0): `value` = whole-job evals/s of the timed steps, `ms_per_step` = milliseconds of one timed step.
+A plain run does only that: set up, warm up, time `--steps` steps, write the outputs of the last one (`--dump-outputs DIR`) and
+print the line. `--full` adds every other leg, each outside the timed region: `roofline` describes the kernel with the largest
+share of a step (HIP events on the launch stream) and the whole step; `verification` checks the line against the oracle;
+`variants` re-times the two other ask populations of SURVEY.md §8d (every ask its own template; adversarial distinct request
+vectors) and configs[4]; `end_to_end` is one cold pass including encode + upload + class build; `cpu_baseline` is the oracle
+on the host cores; `predicates_callback` and `allocation_round` time the per-pair seam and conflict-resolved rounds; at N > 1
+the step without the bitmap gather and the communicators' reports.
 """
 import argparse
 import importlib
@@ -71,7 +75,62 @@ def parse_args():
     ap.add_argument("--no-configs4", action="store_true", help="N=1: leave the configs[4] (100k x 5M, one GPU) leg out of `variants`")
     ap.add_argument("--seed-offset", type=int, default=0, help="added to the workload seed (the configs[4] leg of the default run uses +2)")
     ap.add_argument("--no-verify", action="store_true", help="skip the checks that make every published number self-verifying (verify_leg)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure: roofline profile steps, verification, CPU baselines, callbacks, "
+                         "allocation rounds, variants, end-to-end, the N>1 extras (the --no-* / --cpu-seconds / --profile-steps options "
+                         "shape these legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+DUMP_SEED = 0x44554D50  # "DUMP": the fixed sample of the outputs too large to write whole
+DUMP_ASK_BYTES = 32 << 20  # per-ask arrays (counts, decisions) as float64
+DUMP_ROW_BYTES = 24 << 20  # sampled bitmap rows as float32 0/1
+
+
+def _bits(words, n_bits):
+    """[k][w] 64-bit words → [k][n_bits] float32 0/1, bit j of word i = column 64 i + j (the engine's row layout)."""
+    w = np.ascontiguousarray(words).view(np.uint8).reshape(len(words), -1)
+    return np.unpackbits(w, axis=1, bitorder="little")[:, :n_bits].astype(np.float32)
+
+
+def dump_outputs(path, pm, counts, decisions, gathered=None):
+    """What the timed path handed its caller in the last step: the per-ask feasible counts and bin-pack decisions (whole, or
+    a fixed seeded sample of asks when they exceed DUMP_ASK_BYTES, with `ask_index`), and a fixed seeded sample of bitmap
+    rows — the engine's rows at N = 1, the caller-owned gathered [G][rows][row_stride] bitmap at N > 1 when it is gathered.
+    The decision keys of the N > 1 exchange are its internal encoding, not an answer: they are not written."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    counts = counts.cpu().numpy()
+    decisions = decisions.cpu().numpy()
+    P = len(counts)
+    n_asks = P if 16 * P <= DUMP_ASK_BYTES else DUMP_ASK_BYTES // 24  # (a sample carries its ask_index as a third array)
+    written = {}
+    if n_asks < P:
+        ask = np.sort(rng.choice(P, n_asks, replace=False))
+        counts, decisions = counts[ask], decisions[ask]
+        written["ask_index"] = ask.astype(np.float64)
+    written["counts"] = counts.astype(np.float64)
+    written["decisions"] = decisions.astype(np.float64)
+    lay = pm.layout()
+    if gathered is None:
+        n_rows = int(min(P, 128, max(1, DUMP_ROW_BYTES // (4 * max(lay.num_nodes, 1)))))
+        pods = np.sort(rng.choice(P, n_rows, replace=False)).astype(np.int32)
+        written["bitmap_row_pods"] = pods.astype(np.float64)
+        written["bitmap_rows"] = _bits(pm.read_rows(pods), lay.num_nodes)
+    else:
+        world, rows_cap, stride = gathered.shape
+        n_rows = int(min(rows_cap, 128, max(1, DUMP_ROW_BYTES // (4 * world * stride * 64))))
+        rows = np.sort(rng.choice(rows_cap, n_rows, replace=False))
+        words = gathered[:, torch.from_numpy(rows).to(gathered.device)].cpu().numpy()  # [G][k][stride]
+        written["gathered_rows"] = rows.astype(np.float64)
+        written["gathered_bitmap_rows"] = _bits(words.reshape(world * n_rows, stride), stride * 64).reshape(world, n_rows, stride * 64)
+    for name, arr in written.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def cpu_baseline(pm, budget_s, seed):
@@ -518,6 +577,26 @@ def timed_leg(pkg, dev, stream, a, steps, warmup, profile_steps, **kwok):
     return out
 
 
+def load_package():
+    """The package, its native libraries loaded as build() left them. The package's loader takes a build lock (a file under
+    its lib/) even when nothing needs building, and the benchmark may run as a user who cannot write the tree: when both
+    libraries are newer than every source they are loaded as they are, without the lock. A missing or stale library still
+    goes through the package's own build, which fails loudly where it cannot write."""
+    pkg = importlib.import_module("yunikorn-k8shim_amd")
+    ffi = importlib.import_module("yunikorn-k8shim_amd._ffi")
+    b = pkg.build
+    build_engine, build_host = b.build_engine, b.build_host
+    if not b._stale(b.LIBYKPRED, b.ENGINE_DEPS) and not b._stale(b.LIBYKHOST, b.HOST_DEPS + [b.LIBYKPRED]):
+        b.build_engine = lambda force=False, verbose=False: b.LIBYKPRED
+        b.build_host = lambda force=False, verbose=False: b.LIBYKHOST
+    try:
+        ffi.load_ykpred()  # (loaded once per process: every later manager reuses these handles)
+        ffi.load_ykhost()
+    finally:
+        b.build_engine, b.build_host = build_engine, build_host
+    return pkg
+
+
 def free_port():
     import socket
     with socket.socket() as s:
@@ -526,8 +605,9 @@ def free_port():
 
 
 def launch_ranks(a):
-    """`python bench.py --gpus N` without a launcher: re-executes this script as N ranks of one node (one per GPU) under
-    torch.distributed.run — the same command form the driver uses itself — so that the flag can never silently measure one GPU."""
+    """`python bench.py --gpus N` without a launcher: runs this script as N ranks of one node (one per GPU) under
+    torch.distributed.run in a child process — the same command form the driver uses itself — so that the flag can never
+    silently measure one GPU. This process has asked the runtime for its devices, so it does not replace itself (exec)."""
     backend = os.environ.get("BENCH_BACKEND", "nccl")
     have = torch.cuda.device_count()
     if backend == "nccl" and have < a.gpus:
@@ -536,7 +616,8 @@ def launch_ranks(a):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={a.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    import subprocess
+    sys.exit(subprocess.call(cmd))
 
 
 def main():
@@ -566,7 +647,7 @@ def main():
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
 
-    pkg = importlib.import_module("yunikorn-k8shim_amd")
+    pkg = load_package()
     shard = importlib.import_module("yunikorn-k8shim_amd.sharding")
     strong = world > 1 and not a.weak
     gang = a.gang if a.gang >= 0 else (100 if strong else 0)
@@ -704,21 +785,27 @@ def main():
         elapsed = float(t.item())
     ms_per_step = elapsed / a.steps * 1e3
 
+    if a.dump_outputs and rank == 0:
+        counts, decisions, _ = outs[(step_no[0] - 1) % nbuf]
+        dump_outputs(a.dump_outputs, pm, counts, decisions, gathered=gathered)
+
     lay = pm.layout()
-    # ---- roofline (HIP events on the launch stream, bracketing each kernel)
-    def prof_step(prof):
-        step(profile=prof)
-        drain()
-    kern = profile_kernels(pm, prof_step, a.profile_steps)
-    algo_bytes = algorithmic_bytes(pm, lay)
-    traffic = None
-    if world == 1 and not a.direct and not a.spread and gang == 0:
-        traffic = measured_traffic("unique_request_vectors" if a.unique_requests else ("own_template_per_ask" if a.templates == 0 else
-                                   ("default" if a.templates == 2000 else None)), P, N)
-    roof = roofline_of(kern, algo_bytes, ms_per_step, traffic, lay=lay, b_node=node_row_bytes(pm))
+    kern, roof = {}, None
+    if a.full:
+        # ---- roofline (HIP events on the launch stream, bracketing each kernel)
+        def prof_step(prof):
+            step(profile=prof)
+            drain()
+        kern = profile_kernels(pm, prof_step, a.profile_steps)
+        algo_bytes = algorithmic_bytes(pm, lay)
+        traffic = None
+        if world == 1 and not a.direct and not a.spread and gang == 0:
+            traffic = measured_traffic("unique_request_vectors" if a.unique_requests else ("own_template_per_ask" if a.templates == 0 else
+                                       ("default" if a.templates == 2000 else None)), P, N)
+        roof = roofline_of(kern, algo_bytes, ms_per_step, traffic, lay=lay, b_node=node_row_bytes(pm))
 
     gather = None
-    if do_gather:
+    if do_gather and a.full:
         # extra leg, outside the timed region: the same step without the bitmap gather (shard evaluation + decision exchange)
         gather_on[0] = False
         step()
@@ -766,7 +853,7 @@ def main():
     # ---- the headline number verifies itself (outside the timed region): class rows, sampled classes x all nodes against the
     # oracle incl. decisions, and the independent per-pair kernel's checksum. Shards verify their own slab on the device.
     verification = None
-    if not a.no_verify and not a.direct:
+    if a.full and not a.no_verify and not a.direct:
         try:
             pm.evaluate()
             pm.synchronize()
@@ -778,9 +865,9 @@ def main():
                 verification["ok"] = bool(all(flags))
         except Exception as exc:  # noqa: BLE001 - a failed CHECK must show in the line, not take it down
             verification = {"ok": False, "error": str(exc)}
-    cpu = cpu_baseline(pm, a.cpu_seconds, SEED) if rank == 0 else None
+    cpu = cpu_baseline(pm, a.cpu_seconds, SEED) if a.full and rank == 0 else None
     callbacks = rounds = None
-    if rank == 0 and world == 1 and not a.no_variants and not a.direct:
+    if a.full and rank == 0 and world == 1 and not a.no_variants and not a.direct:
         try:
             callbacks = predicates_callback_leg(pm, P, N)
         except Exception as exc:  # noqa: BLE001 — a side leg never takes the line down
@@ -796,7 +883,7 @@ def main():
     except Exception:  # noqa: BLE001
         routing = None
     comm_report = None
-    if world > 1:
+    if a.full and world > 1:
         # what every rank's engine says about its communicator (ykpred_comm_info): rank, world and first node of the shard — the
         # first multi-GPU run shows at a glance that N communicators of world N exist and that the shards tile the cluster
         mine = dict(zip(("rank", "world", "node_offset"), pm.comm_info())) if use_abi else {"rank": rank, "world": world, "node_offset": first, "c_abi": False}
@@ -811,7 +898,7 @@ def main():
     torch.cuda.empty_cache()
 
     variants = end_to_end = None
-    if rank == 0 and world == 1 and not a.no_variants and not a.direct:
+    if a.full and rank == 0 and world == 1 and not a.no_variants and not a.direct:
         base = dict(seed=SEED + 2, num_nodes=a.nodes, num_pods=a.pods, node_affinity=0 if a.no_affinity else 1, spread=1 if a.spread else 0)
         variants = {}
         for name, kw in (("own_template_per_ask", dict(num_templates=0)),
@@ -888,7 +975,7 @@ def main():
             out["decisions_only"] = {"ms_per_step": gather["step_without_gather_ms"], "evals_per_sec": gather["evals_per_sec_without_gather"],
                                      "decisions_per_sec": float(P) / (gather["step_without_gather_ms"] * 1e-3), "link_bytes_per_ask": 16,
                                      "note": "measured outside the timed region of this line (same engine, same outputs, gather switched off)"}
-        elif world > 1:
+        elif world > 1 and not do_gather:
             out["decisions_only"] = {"ms_per_step": ms_per_step, "evals_per_sec": evals / elapsed, "decisions_per_sec": float(P) * a.steps / elapsed,
                                      "link_bytes_per_ask": 16, "note": "this line: the bitmap gather is not in the step"}
         if variants is not None:

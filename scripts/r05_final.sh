@@ -5,7 +5,7 @@
 O=gpurun_out/r05_final; mkdir -p $O
 ROOT="$GRAFT_REPO_ROOT"; cd "$ROOT" || exit 1
 timeout 1000 python -m pytest tests -x -q -m gpu --durations=6 > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -9 $O/pytest_gpu.log
-timeout 500 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -2 $O/bench.err
+timeout 500 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -2 $O/bench.err
 timeout 300 python scripts/bench_rounds.py --configs4 > $O/rounds.json 2> $O/rounds.err; echo "rounds rc=$?"
 hipcc --offload-arch=gfx950 -O3 "$ROOT/scripts/pmc_calibration_fill.hip" -o /tmp/fill_probe 2>/dev/null
 cd /tmp && export TMPDIR=/tmp

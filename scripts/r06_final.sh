@@ -7,7 +7,7 @@ ROOT="$GRAFT_REPO_ROOT"; cd "$ROOT" || exit 1
 if [ "${1:-}" != "skip-suite" ]; then
   timeout 1200 python -m pytest tests -x -q -m gpu --durations=6 > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -9 $O/pytest_gpu.log
 fi
-timeout 700 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -2 $O/bench.err
+timeout 700 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -2 $O/bench.err
 hipcc --offload-arch=gfx950 -O3 "$ROOT/scripts/pmc_calibration_fill.hip" -o /tmp/fill_probe 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
 P="$ROOT/$O/pmc"; mkdir -p "$P"

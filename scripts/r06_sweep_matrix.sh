@@ -3,7 +3,7 @@
 # Usage on the GPU box: bash scripts/r06_sweep_matrix.sh "<min_run values>" "<group values>"
 O=gpurun_out/r06_sweep; mkdir -p $O
 for M in ${1:-2}; do for G in ${2:-0}; do
-  YKPRED_TUNE="sweep_min_run=$M,sweep_groups=$G" timeout 300 python bench.py --steps 10 --cpu-seconds 0 --no-variants --no-ingest --templates 0 --unique-requests > $O/u_m${M}_g$G.json 2> $O/u_m${M}_g$G.err || tail -3 $O/u_m${M}_g$G.err
+  YKPRED_TUNE="sweep_min_run=$M,sweep_groups=$G" timeout 300 python bench.py --full --steps 10 --cpu-seconds 0 --no-variants --no-ingest --templates 0 --unique-requests > $O/u_m${M}_g$G.json 2> $O/u_m${M}_g$G.err || tail -3 $O/u_m${M}_g$G.err
   python - <<PY
 import json
 d=json.load(open("$O/u_m${M}_g$G.json")); k=d.get("kernel_ms",{})

@@ -22,7 +22,7 @@ print(torch.cuda.device_count())
 PY
 )
 if [ "$GPUS" -lt 2 ]; then echo "scale_check: $GPUS GPU(s) visible, nothing to scale over"; exit 2; fi
-python bench.py --gpus 1 --no-variants --cpu-seconds 0 > "$OUT/n1.json" 2> "$OUT/n1.err" || { echo "world 1 bench failed"; tail -5 "$OUT/n1.err"; exit 1; }
+python bench.py --gpus 1 --full --no-variants --cpu-seconds 0 > "$OUT/n1.json" 2> "$OUT/n1.err" || { echo "world 1 bench failed"; tail -5 "$OUT/n1.err"; exit 1; }
 RC=0
 for W in 2 4 8; do
   [ "$W" -le "$GPUS" ] || continue
@@ -40,8 +40,8 @@ for W in 2 4 8; do
   else
     grep "^rank" "$OUT/rounds_w$W.log"
   fi
-  timeout 900 python bench.py --gpus "$W" --cpu-seconds 0 > "$OUT/n${W}_gathered.json" 2> "$OUT/n${W}_gathered.err" || { echo "   gathered bench failed"; RC=1; }
-  timeout 900 python bench.py --gpus "$W" --no-gather --cpu-seconds 0 > "$OUT/n${W}_decisions_only.json" 2> "$OUT/n${W}_decisions_only.err" || { echo "   decisions-only bench failed"; RC=1; }
+  timeout 900 python bench.py --gpus "$W" --full --cpu-seconds 0 > "$OUT/n${W}_gathered.json" 2> "$OUT/n${W}_gathered.err" || { echo "   gathered bench failed"; RC=1; }
+  timeout 900 python bench.py --gpus "$W" --full --no-gather --cpu-seconds 0 > "$OUT/n${W}_decisions_only.json" 2> "$OUT/n${W}_decisions_only.err" || { echo "   decisions-only bench failed"; RC=1; }
 done
 python - "$OUT" <<'PY'
 import glob, json, os, sys

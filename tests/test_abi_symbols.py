@@ -2,6 +2,7 @@
 include/*.h declares; and the product fails loudly (no CPU fallback) when no HIP device is present."""
 import ctypes
 import importlib
+import json
 import os
 import re
 
@@ -123,20 +124,39 @@ def test_cgo_call_sequence_replays_on_the_device(tmp_path):
     assert out.returncode == 0 and "replay ok (device 0)" in out.stdout, (out.stdout[-500:], out.stderr[-3000:])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="the reference tree is only present in the build container")
-def test_go_patches_apply_to_the_reference():
+def test_go_patches_apply_to_the_reference(tmp_path):
     """integration/patches/*.diff (scripts/make_go_patches.py): the install line of context.go:130, the observer hooks of
-    scheduler_cache.go:148-484 and the service.predicateEngine key of schedulerconf.go:59-81 apply cleanly to the reference,
-    and are what the generator produces from it today."""
+    scheduler_cache.go:148-484 and the service.predicateEngine key of schedulerconf.go:59-81 apply cleanly to the reference.
+    tests/golden/go_patch_preimages.json holds, per edited file, its line count in the reference and the SHA-256 of the lines
+    each hunk replaces, at the hunk's position: every hunk's pre-image must hash to them, and `git apply --check` must accept
+    the patches on a stand-in of each file with those lines in those places."""
     import shutil
     import subprocess
+    import sys
     if not shutil.which("git"):
         pytest.skip("git not installed")
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_go_patch_preimages as pre
     pdir = os.path.join(ROOT, "integration", "patches")
     names = sorted(n for n in os.listdir(pdir) if n.endswith(".diff"))
     assert names == ["context.go.diff", "scheduler_cache.go.diff", "schedulerconf.go.diff"]
+    with open(os.path.join(ROOT, "tests", "golden", "go_patch_preimages.json")) as f:
+        golden = json.load(f)
+    assert sorted(golden) == names
     for n in names:
-        r = subprocess.run(["git", "apply", "--check", "--verbose", os.path.join(pdir, n)], cwd="/root/reference", capture_output=True, text=True)
+        target, hunks = pre.hunks(open(os.path.join(pdir, n)).read())
+        want = golden[n]
+        assert target == want["target"] and len(hunks) == len(want["hunks"]) > 0, n
+        stand_in = [f"// line {i + 1} of {target}" for i in range(want["lines"])]
+        for (start, old_len, _, new_len, old, new), h in zip(hunks, want["hunks"]):
+            assert (start, old_len) == (h["old_start"], h["old_len"]) and len(old) == old_len and len(new) == new_len, (n, start)
+            assert pre.digest(old) == h["sha256"], f"{n}: the hunk at line {start} does not meet the reference's lines there"
+            stand_in[start - 1:start - 1 + old_len] = old
+        assert len(stand_in) == want["lines"], n
+        path = tmp_path / target
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text("".join(line + "\n" for line in stand_in))
+        r = subprocess.run(["git", "apply", "--check", "--verbose", os.path.join(pdir, n)], cwd=tmp_path, capture_output=True, text=True)
         assert r.returncode == 0, (n, r.stderr)
     # the Go file and the patches agree on the names they share
     go = open(os.path.join(ROOT, "integration", "gpu_predicate_manager.go")).read()

@@ -1390,7 +1390,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path, weak):
     env = dict(os.environ, BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", "29577", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--nodes", "4000", "--pods", "50000", "--cpu-seconds", "0", "--profile-steps", "1"] + (["--weak"] if weak else [])
+           "--nodes", "4000", "--pods", "50000", "--cpu-seconds", "0", "--profile-steps", "1", "--full"] + (["--weak"] if weak else [])
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
@@ -1652,7 +1652,7 @@ def test_bench_gpus_flag_launches_the_ranks_itself():
     ranks. On this one-GPU box the ranks share cuda:0 and the exchanges take the torch.distributed reference forms (gloo);
     with the default backend the same command must REFUSE rather than measure one GPU and call it two."""
     import torch
-    small = ["--steps", "2", "--warmup", "1", "--nodes", "4000", "--pods", "50000", "--cpu-seconds", "0", "--profile-steps", "1"]
+    small = ["--steps", "2", "--warmup", "1", "--nodes", "4000", "--pods", "50000", "--cpu-seconds", "0", "--profile-steps", "1", "--full"]
     out, d = _bench(["--gpus", "2"] + small, env={"BENCH_BACKEND": "gloo"})
     assert out.returncode == 0, out.stderr[-2000:]
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["total_nodes"] == 4000 and d["config"]["gang_size"] == 100
@@ -1663,6 +1663,33 @@ def test_bench_gpus_flag_launches_the_ranks_itself():
     out, d = _bench(["--gpus", "1", "--no-variants"] + small)
     assert out.returncode == 0, out.stderr[-2000:]
     assert d["n_gpus"] == 1 and d["scaling"] is None and d["value"] > 0
+
+
+def test_bench_plain_line_dumps_the_last_step(tmp_path):
+    """A plain bench run times exactly --steps steps, runs none of the --full legs, and --dump-outputs writes what the last
+    step computed: counts and decisions of every ask and the sampled bitmap rows equal a fresh engine's on the same workload."""
+    out, d = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--nodes", "4000", "--pods", "50000", "--dump-outputs", str(tmp_path)])
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "evals/s" and d["higher_is_better"] is True and d["dtype"] == "int64"
+    assert d["verification"] is None and d["roofline"] is None and d["cpu_baseline"] is None and d["kernel_ms"] == {}
+    assert "variants" not in d and "allocation_round" not in d and "predicates_callback" not in d
+    files = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(files) == {"counts", "decisions", "bitmap_rows", "bitmap_row_pods"}
+    assert all(v.dtype in (np.float32, np.float64) for v in files.values())
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64 << 20
+    m = pkg.GpuPredicateManager(device=0)
+    try:
+        m.generate_kwok(seed=0x59554E49 + 2, num_nodes=4000, num_pods=50000, num_templates=2000, node_affinity=1, unique_requests=0, spread=0,
+                        gang_size=0, node_index_offset=0, total_nodes=4000)
+        m.evaluate()
+        m.synchronize()
+        assert np.array_equal(files["counts"], m.read_counts()) and np.array_equal(files["decisions"], m.read_decisions())
+        pods = files["bitmap_row_pods"].astype(np.int32)
+        assert len(pods) > 0
+        assert np.array_equal(files["bitmap_rows"], unpack(m.read_rows(pods), 4000).astype(np.float32))
+    finally:
+        m.close()
 
 
 @pytest.mark.skipif("__import__('torch').cuda.device_count() < 2")
@@ -1677,7 +1704,8 @@ def test_rccl_world_two_through_the_c_abi():
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-2500:])
     assert out.stdout.count(" rccl: rows True counts True decisions True") == 2, out.stdout[-1500:]
-    _, d = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--nodes", "8000", "--pods", "100000", "--cpu-seconds", "0", "--profile-steps", "1"])
+    _, d = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--nodes", "8000", "--pods", "100000", "--cpu-seconds", "0", "--profile-steps", "1",
+                   "--full"])
     assert d["n_gpus"] == 2 and d["config"]["collectives"] == "c-abi rccl"
 
 

@@ -398,6 +398,7 @@ def test_parallel_ingest_under_thread_sanitizer(cluster_docs, tmp_path):
     placement — every one on the host's cores: >= 65 536 asks of their own templates) and two concurrent reader threads on the same
     handle produce no data-race report."""
     import os
+    import shutil
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     lib = os.path.join(root, "yunikorn-k8shim_amd", "lib")
@@ -417,7 +418,13 @@ def test_parallel_ingest_under_thread_sanitizer(cluster_docs, tmp_path):
                            "-o", str(tmp_path / "ingest_tsan.o")])
     subprocess.check_call(["g++", "-std=c++17"] + san + ["-I" + os.path.join(root, "include"), os.path.join(root, "yunikorn-k8shim_amd", "csrc", "host", "host.cpp"),
                            str(tmp_path / "ingest_tsan.o"), "-o", exe, "-L" + lib, "-lykpred", "-lpthread", "-Wl,-rpath," + lib])
-    out = subprocess.run([exe] + paths, capture_output=True, text=True, timeout=600,
+    cmd = [exe] + paths
+    # ThreadSanitizer's fixed shadow layout cannot take every address a kernel with high mmap randomisation hands out ("FATAL:
+    # ThreadSanitizer: unexpected memory mapping"): the binary runs with address-space randomisation off for itself (setarch -R)
+    arch = os.uname().machine
+    if shutil.which("setarch") and subprocess.run(["setarch", arch, "-R", "true"], capture_output=True).returncode == 0:
+        cmd = ["setarch", arch, "-R"] + cmd
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600,
                          env=dict(os.environ, YKHOST_INGEST_THREADS="4", TSAN_OPTIONS="halt_on_error=0:report_signal_unsafe=0"))
     assert out.returncode == 0 and "ingest ok" in out.stdout and "bulk batches 2" in out.stdout, (out.stdout[-500:], out.stderr[-3000:])
     assert "WARNING: ThreadSanitizer" not in out.stderr, out.stderr[-4000:]
