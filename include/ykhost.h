@@ -156,6 +156,19 @@ ykpred_engine_t* ykhost_engine(ykhost_t* h); /* the underlying engine, for layou
 int32_t ykhost_set_row_stride(ykhost_t* h, int32_t words /* multiple of 16; 0 = automatic */);
 int32_t ykhost_set_row_capacity(ykhost_t* h, int32_t rows /* physical bitmap rows every shard allocates; 0 = automatic */);
 int32_t ykhost_comm_init(ykhost_t* h, const uint8_t* id /* [YKPRED_COMM_ID_BYTES] */, int32_t rank, int32_t world, int32_t node_offset);
+/* The shards' topology dictionaries are made cluster-wide inside ykhost_comm_init: every shard exports its node-side share
+ * (the values of every topology key on its nodes, the templates of its pods that carry required anti-affinity terms, its first
+ * and last NodeID), the shards all-gather the exports (ykpred_comm_allgather_bytes), and each keeps the union as the floor of
+ * every later re-encode — domain id d is the same value and count class s the same class on every shard, so the histograms
+ * the engine sums line up cell by cell. When the union changes the dictionary shape the engine is re-created and adopts the
+ * communicator (ykpred_comm_adopt); the digest of the dictionaries goes to the engine (ykpred_set_dictionary_digest). The merge also checks the name-sorted contract (every
+ * NodeID of shard r sorts before every NodeID of shard r + 1) and refuses, on every rank alike, when it is broken.
+ * The two halves are callable on their own (mirror-only handles included):
+ *   ykhost_topology_export  this shard's export; returns the required length (like dump_snapshot). Not a pure query: a
+ *                           device handle syncs first (uploads what changed), a mirror-only handle re-encodes its objects
+ *   ykhost_topology_merge   `len` bytes of every shard's export in rank order, each followed by a NUL byte */
+int64_t ykhost_topology_export(ykhost_t* h, char* out, int64_t len);
+int32_t ykhost_topology_merge(ykhost_t* h, const char* blobs, int64_t len);
 int32_t ykhost_comm_destroy(ykhost_t* h);
 
 /* batched evaluation of every pending ask against every node: phase selects the plugin lists */

@@ -139,8 +139,9 @@ typedef struct ykpred_nodes {
   const int32_t* name_rank;      /* [count]      position of the node's NodeID in lexicographic order: the tie-break of the
                                                  bin-pack order between nodes of equal score (yunikorn-core sorts by score,
                                                  then node id). NULL = ties by node index. In a node-sharded cluster the
-                                                 shards are ranges of a name-sorted node list, so that the cross-shard
-                                                 tie-break (global node index) agrees with it. */
+                                                 shards are ranges of a name-sorted node list, in any insertion order
+                                                 inside a shard: between shards the tie-break is the shard (lower rank
+                                                 first), inside one this rank — together the cluster's NodeID order. */
 } ykpred_nodes_t;
 
 /* One topology constraint of a pod spec: a hard (DoNotSchedule) topology spread constraint, or one InterPodAffinity
@@ -464,7 +465,10 @@ int32_t ykpred_preemption_batch(ykpred_engine_t* e, int32_t num_queries, const i
  *                           feasible node in bin-pack order, ties by global node index (MIN key, then MIN index), -1 = none
  *   PodTopologySpread / InterPodAffinity histograms: once a communicator is attached, ykpred_eval itself sums the
  *                           per-shard histograms (SUM of matches, MAX of "domain present") between its count and min
- *                           passes — the shards must share the topology-domain dictionaries — and ykpred_query /
+ *                           passes — the shards must share the topology-domain dictionaries (ykhost_comm_init makes
+ *                           them cluster-wide; the ranks compare the histograms' shape and dictionary digest first and,
+ *                           when they differ, all return the same YKPRED_E_INVALID instead of summing misaligned cells;
+ *                           that check is one more small all-gather and a host sync per histogram sum) — and ykpred_query /
  *                           ykpred_preemption reuse those cluster-wide histograms instead of rebuilding shard-local ones.
  * Not sharded: PreemptionPredicates (one node, sequential victim prefix) runs on the shard that owns the node. */
 #define YKPRED_COMM_ID_BYTES 128
@@ -476,6 +480,18 @@ int32_t ykpred_comm_use_library(const char* path);
 int32_t ykpred_comm_unique_id(uint8_t* id /* [YKPRED_COMM_ID_BYTES] */);
 int32_t ykpred_comm_init(ykpred_engine_t* e, const uint8_t* id, int32_t rank, int32_t world, int32_t node_offset);
 int32_t ykpred_comm_destroy(ykpred_engine_t* e);
+/* All-gather of `bytes` HOST bytes over the attached communicator: recv (host, [world][bytes]) gets every rank's `send`, in
+ * rank order. Collective; every rank passes the same `bytes` (a host that ships blobs of unequal length gathers the lengths
+ * first). What the hosts exchange at comm_init (ykhost_comm_init: the shards' topology-domain values) travels this way. */
+int32_t ykpred_comm_allgather_bytes(ykpred_engine_t* e, const void* send, int64_t bytes, void* recv);
+/* Moves the communicator (with rank, world and node offset) of `from` to `to`, an engine on the same device without one: what a
+ * host does when its dictionaries change shape on a node-sharded handle and it re-creates the engine (the communicator cannot be
+ * initialised twice from one id). `from` is left without a communicator. */
+int32_t ykpred_comm_adopt(ykpred_engine_t* to, ykpred_engine_t* from);
+/* A digest of what the topology ids stand for (the host's topology key strings, domain values in id order, selector classes).
+ * Node-sharded ranks compare it, with the histogram shape, before they sum histograms or start a round: equal counts over
+ * different dictionaries are refused (YKPRED_E_INVALID on every rank) instead of summed. 0 = not provided. */
+int32_t ykpred_set_dictionary_digest(ykpred_engine_t* e, uint64_t digest);
 /* the attached communicator's geometry (rank 0, world 1, node_offset 0 without one); any of the pointers may be NULL */
 int32_t ykpred_comm_info(const ykpred_engine_t* e, int32_t* rank, int32_t* world, int32_t* node_offset);
 /* Rows of the NEXT ykpred_set_nodes get this stride (64-bit words, multiple of 16, >= the shard's own need); 0 = automatic.

@@ -109,3 +109,72 @@ def small_slots(seed, n_nodes=3000, n_pods=12000, n_templates=24, spread=False, 
         name, spec = rng.choice(templates)
         pods.append({"metadata": {"name": f"ask-{k}", "uid": f"ask-{k}", "namespace": "default", "labels": {"app": name}}, "spec": dict(spec)})
     return {"nodes": nodes, "pods": pods}
+
+
+def sharded_mixed(seed, world, n_nodes=240, n_pods=600, ties=True, zones_by_range=True, spread=True, ipa=True, resident_anti=False,
+                  ports=True, pin=True):
+    """A cluster for node-sharded engines whose shards DIFFER, cut the documented way: nodes sorted by name, cut with
+    sharding.shard_ranges, each shard inserted in a shuffled order. → (snapshot, shards): the snapshot's node list is the
+    concatenation of the shards (cluster index = shard offset + local index), shards[r] = that shard's node list.
+      unpadded names (node-9 sorts after node-10); `ties`: most nodes identical and empty, so keys tie inside and across shards;
+      `zones_by_range`: zone by name range — some zones exist on one shard only, one zone has a single node;
+      `spread`: hard spread on zone and on hostname; `ipa`: required pod (anti)affinity on hostname and zone, between asks and
+      towards resident pods; `resident_anti`: resident pods with anti-affinity terms (they sit on one shard only);
+      `ports`: host ports; `pin`: one ask pinned by nodeName."""
+    import importlib
+    sharding = importlib.import_module("yunikorn-k8shim_amd.sharding")
+    rng = random.Random(seed)
+    names = sorted(f"node-{i}" for i in range(n_nodes))  # name order: node-0, node-1, node-10, node-100, ...
+    zone_of = {}
+    for i, name in enumerate(names):
+        if zones_by_range:  # contiguous name ranges: with world >= 2 the first and last zones live on one shard each
+            zone_of[name] = "z-solo" if i == n_nodes // 2 else f"z{(i * 7) // n_nodes}"
+        else:
+            zone_of[name] = f"z{rng.randrange(4)}"
+    nodes = {}
+    for i, name in enumerate(names):
+        if ties and rng.random() < 0.8:
+            alloc = {"cpu": "8", "memory": "16Gi", "pods": "20"}
+        else:
+            alloc = {"cpu": rng.choice(["4", "8", "16"]), "memory": rng.choice(["8Gi", "16Gi", "32Gi"]), "pods": rng.choice(["5", "10", "110"])}
+        node = {"metadata": {"name": name, "labels": {"zone": zone_of[name], "kubernetes.io/hostname": name}},
+                "spec": {"taints": []}, "status": {"allocatable": alloc}, "pods": []}
+        if not ties or rng.random() < 0.15:
+            for j in range(rng.choice([1, 2])):
+                pod = {"metadata": {"name": f"r-{name}-{j}", "uid": f"r-{name}-{j}", "namespace": "default", "labels": {"app": rng.choice(["w", "v"])}},
+                       "spec": {"containers": [{"name": "c", "resources": {"requests": {"cpu": rng.choice(["100m", "1"]), "memory": "256Mi"}}}]}}
+                if resident_anti and i < n_nodes // (2 * world):  # on the first shard only
+                    pod["spec"]["affinity"] = {"podAntiAffinity": {"requiredDuringSchedulingIgnoredDuringExecution": [
+                        {"labelSelector": {"matchLabels": {"app": rng.choice(["t0", "t1"])}}, "topologyKey": rng.choice(["zone", "kubernetes.io/hostname"])}]}}
+                node["pods"].append(pod)
+        nodes[name] = node
+    templates = []
+    for t in range(8):
+        req = {"cpu": rng.choice(["250m", "500m", "1", "2"]), "memory": rng.choice(["512Mi", "1Gi", "2Gi"])}
+        spec = {"containers": [{"name": "c", "resources": {"requests": req}}]}
+        if spread and t % 4 == 1:
+            spec["topologySpreadConstraints"] = [{"maxSkew": rng.choice([1, 2]), "topologyKey": rng.choice(["zone", "kubernetes.io/hostname"]),
+                                                  "whenUnsatisfiable": "DoNotSchedule", "labelSelector": {"matchLabels": {"app": f"t{t}"}}}]
+        if ipa and t % 4 in (2, 3):
+            term = lambda key: {"labelSelector": {"matchLabels": {"app": rng.choice([f"t{t}", "t0", "w", "v"])}}, "topologyKey": key}
+            aff = {"podAntiAffinity": {"requiredDuringSchedulingIgnoredDuringExecution": [term("kubernetes.io/hostname")]}}
+            if t % 4 == 3:
+                aff["podAffinity"] = {"requiredDuringSchedulingIgnoredDuringExecution": [term("zone")]}
+                aff["podAntiAffinity"]["requiredDuringSchedulingIgnoredDuringExecution"].append(term("zone"))
+            spec["affinity"] = aff
+        if ports and t == 5:
+            spec["containers"][0]["ports"] = [{"hostPort": 8080, "containerPort": 80}]
+        templates.append((f"t{t}", spec))
+    pods = []
+    for k in range(n_pods):
+        name, spec = templates[rng.randrange(len(templates))] if rng.random() < 0.7 else templates[k % 2]
+        spec = {kk: (list(vv) if isinstance(vv, list) else vv) for kk, vv in spec.items()}
+        if pin and k == n_pods // 3:
+            spec["nodeName"] = names[-1]
+        pods.append({"metadata": {"name": f"ask-{k}", "uid": f"ask-{k}", "namespace": "default", "labels": {"app": name}}, "spec": spec})
+    shards = []
+    for first, count in sharding.shard_ranges(n_nodes, world):
+        part = [nodes[n] for n in names[first:first + count]]
+        rng.shuffle(part)  # insertion order inside a shard is NOT name order
+        shards.append(part)
+    return {"nodes": [n for part in shards for n in part], "pods": pods}, shards

@@ -8,6 +8,9 @@
 // forms, ordering after the work already queued on the stream) over a POSIX shared-memory segment: every rank copies its
 // contribution into its slot, a barrier, every rank reads the slots. ykpred_comm_use_library() points the engine at it.
 // It is slow on purpose (synchronous, through host memory): what it proves is argument marshalling, layouts and ordering.
+// It is also STRICTER than RCCL about agreement: every rank records (count, type, op) of its call in the segment's header, and
+// when the ranks disagree — or one of them could not stage its contribution — EVERY rank returns ncclInvalidArgument, after
+// both barriers, instead of reducing or copying stale slot bytes (RCCL would hang or read garbage).
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -23,11 +26,17 @@
 namespace {
 constexpr size_t kSlotBytes = (size_t)96 << 20;  // per rank (sparse: only what a test touches is ever backed by memory)
 constexpr int kMaxRanks = 8;
+struct Call {  // what a rank passed to the collective it is in (ok = 0: it could not stage its contribution)
+  uint64_t count;
+  int32_t type, op, ok, pad;
+};
 struct Header {
   std::atomic<int> arrived;
   std::atomic<int> generation;
   std::atomic<int> attached;
+  Call call[kMaxRanks];
 };
+static_assert(sizeof(Header) <= 4096, "the header fits the segment's first page");
 struct Comm {
   int rank = 0, world = 1;
   std::string name;
@@ -53,6 +62,22 @@ size_t type_size(ncclDataType_t t) {
     case ncclInt64: case ncclUint64: case ncclFloat64: return 8;
     default: return 0;
   }
+}
+// Records this rank's call, waits for everybody, and tells whether every rank made the same call and staged its part.
+// Either way every rank has passed the first barrier; the caller passes the second one before it returns.
+bool agree(Comm* c, size_t count, ncclDataType_t type, int op, bool ok) {
+  Call& mine = c->hdr()->call[c->rank];
+  mine.count = count;
+  mine.type = (int32_t)type;
+  mine.op = op;
+  mine.ok = ok ? 1 : 0;
+  barrier(c);
+  const Call& first = c->hdr()->call[0];
+  for (int r = 0; r < c->world; ++r) {
+    const Call& o = c->hdr()->call[r];
+    if (!o.ok || o.count != first.count || o.type != first.type || o.op != first.op) return false;
+  }
+  return true;
 }
 template <class T>
 void reduce_into(T* acc, const T* in, size_t n, ncclRedOp_t op) {
@@ -109,25 +134,34 @@ ncclResult_t ncclCommDestroy(ncclComm_t comm) {
 
 ncclResult_t ncclAllGather(const void* send, void* recv, size_t count, ncclDataType_t type, ncclComm_t comm, hipStream_t stream) {
   Comm* c = (Comm*)comm;
+  if (!c) return ncclInvalidArgument;
   const size_t bytes = count * type_size(type);
-  if (!c || type_size(type) == 0 || bytes > kSlotBytes) return ncclInvalidArgument;
-  if (hipStreamSynchronize(stream) != hipSuccess) return ncclUnhandledCudaError;  // ordered after the work queued on the stream
-  if (bytes && hipMemcpy(c->slot(c->rank), send, bytes, hipMemcpyDeviceToHost) != hipSuccess) return ncclUnhandledCudaError;
-  barrier(c);
-  for (int r = 0; r < c->world && bytes; ++r)
-    if (hipMemcpy((char*)recv + (size_t)r * bytes, c->slot(r), bytes, hipMemcpyHostToDevice) != hipSuccess) return ncclUnhandledCudaError;
+  bool ok = type_size(type) != 0 && bytes <= kSlotBytes;
+  ok = ok && hipStreamSynchronize(stream) == hipSuccess;  // ordered after the work queued on the stream
+  ok = ok && (!bytes || hipMemcpy(c->slot(c->rank), send, bytes, hipMemcpyDeviceToHost) == hipSuccess);
+  if (!agree(c, count, type, -1, ok)) {
+    barrier(c);
+    return ncclInvalidArgument;
+  }
+  ncclResult_t res = ncclSuccess;
+  for (int r = 0; r < c->world && bytes && res == ncclSuccess; ++r)
+    if (hipMemcpy((char*)recv + (size_t)r * bytes, c->slot(r), bytes, hipMemcpyHostToDevice) != hipSuccess) res = ncclUnhandledCudaError;
   barrier(c);  // nobody overwrites a slot before everybody has read it
-  return ncclSuccess;
+  return res;
 }
 
 ncclResult_t ncclAllReduce(const void* send, void* recv, size_t count, ncclDataType_t type, ncclRedOp_t op, ncclComm_t comm, hipStream_t stream) {
   Comm* c = (Comm*)comm;
+  if (!c) return ncclInvalidArgument;
   const size_t bytes = count * type_size(type);
-  if (!c || bytes > kSlotBytes || (op != ncclSum && op != ncclMax && op != ncclMin)) return ncclInvalidArgument;
-  if (type != ncclInt32 && type != ncclInt64 && type != ncclUint64) return ncclInvalidArgument;
-  if (hipStreamSynchronize(stream) != hipSuccess) return ncclUnhandledCudaError;
-  if (bytes && hipMemcpy(c->slot(c->rank), send, bytes, hipMemcpyDeviceToHost) != hipSuccess) return ncclUnhandledCudaError;
-  barrier(c);
+  bool ok = bytes <= kSlotBytes && (op == ncclSum || op == ncclMax || op == ncclMin) && (type == ncclInt32 || type == ncclInt64 || type == ncclUint64);
+  ok = ok && hipStreamSynchronize(stream) == hipSuccess;
+  ok = ok && (!bytes || hipMemcpy(c->slot(c->rank), send, bytes, hipMemcpyDeviceToHost) == hipSuccess);
+  if (!agree(c, count, type, (int)op, ok)) {
+    barrier(c);
+    return ncclInvalidArgument;
+  }
+  ncclResult_t res = ncclSuccess;
   if (bytes) {
     char* acc = new char[bytes];
     memcpy(acc, c->slot(0), bytes);
@@ -138,10 +172,10 @@ ncclResult_t ncclAllReduce(const void* send, void* recv, size_t count, ncclDataT
     }
     const hipError_t s = hipMemcpy(recv, acc, bytes, hipMemcpyHostToDevice);
     delete[] acc;
-    if (s != hipSuccess) return ncclUnhandledCudaError;
+    if (s != hipSuccess) res = ncclUnhandledCudaError;
   }
   barrier(c);
-  return ncclSuccess;
+  return res;
 }
 
 const char* ncclGetErrorString(ncclResult_t r) {

@@ -366,3 +366,31 @@ def test_allocation_rounds_on_a_node_sharded_cluster(tmp_path, world, total_node
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-2500:])
     assert out.stdout.count("sharded rounds True on_device True") == world, (out.stdout[-1500:], out.stderr[-1500:])
 
+
+
+@pytest.mark.parametrize("world", [2, 3])
+@pytest.mark.parametrize("case", ["ties", "zones", "hostname", "everything"])
+def test_node_sharded_engines_on_shards_that_differ(tmp_path, world, case):
+    """Node-sharded engines (world 2 and 3, the collectives through tests/c/rccl_stub.cpp) on shards cut the documented way — ranges
+    of the name-sorted node list — that do NOT look alike (tests/_seqgen.py sharded_mixed): unpadded names inserted in shuffled
+    order inside each shard, so cluster index order is not NodeID order; identical empty nodes whose keys tie within and across
+    shards (ties: the batched replay must break them by (shard, NodeID rank), not by cluster index); zone values that exist on one
+    shard only (zones) and hostname-keyed pod (anti)affinity (hostname): the shards' topology dictionaries are made cluster-wide at
+    comm_init, or their histograms would be summed misaligned; resident pods with anti-affinity terms on the first shard only
+    (hostname, everything): their count classes must exist, numbered alike, on every shard. Every rank checks the gathered rows,
+    counts, decisions and two batched rounds against the ORACLE on the whole cluster, then one collective incremental step
+    against the oracle on the changed cluster, and — with a zone key — that a node update bringing a zone to one shard only makes
+    the next collective step fail with the same error on every rank (tests/_shard_mixed_worker.py)."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    stub = str(tmp_path / "librccl_stub.so")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O1", "-fPIC", "-shared", "-std=c++17", os.path.join(root, "tests", "c", "rccl_stub.cpp"), "-o", stub, "-lrt"])
+    port = 29900 + world * 13 + ["ties", "zones", "hostname", "everything"].index(case)
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
+           "--master-port", str(port), os.path.join(root, "tests", "_shard_mixed_worker.py"), case, "17"]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, SHARD_RCCL_STUB=stub))
+    assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-2500:])
+    assert out.stdout.count("rows True counts True decisions True compressed True rounds True on_device True incremental True mismatch True") == world, \
+        out.stdout[-2000:]

@@ -109,6 +109,7 @@ def load_ykpred():
     L.ykpred_comm_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
     L.ykpred_comm_destroy.argtypes = [C.c_void_p]
     L.ykpred_comm_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.ykpred_comm_allgather_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.ykpred_set_row_stride.argtypes = [C.c_void_p, C.c_int32]
     L.ykpred_set_row_capacity.argtypes = [C.c_void_p, C.c_int32]
     L.ykpred_gather_bitmap.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -171,6 +172,9 @@ def load_ykhost():
     L.ykhost_set_row_capacity.argtypes = [C.c_void_p, C.c_int32]
     L.ykhost_comm_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
     L.ykhost_comm_destroy.argtypes = [C.c_void_p]
+    L.ykhost_topology_export.restype = C.c_int64
+    L.ykhost_topology_export.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
+    L.ykhost_topology_merge.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
     L.ykhost_sync.argtypes = [C.c_void_p]
     L.ykhost_encoded_tables_json.restype = C.c_int64
     L.ykhost_encoded_tables_json.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]

@@ -273,6 +273,9 @@ struct ykpred_engine {
   int sweep_rows[ykk::kMaxIdxRows] = {0, 0}, sweep_row_off[ykk::kMaxIdxRows + 1] = {0, 0, 0}, sweep_runs = 0;  // per walked dimension
   int index_rows_needed = 0;         // index rows some class OUTSIDE the sweep runs reads (the full pass walks only those)
   DevBuf d_agree;  // sharded rounds: what the ranks agree on before the first batch
+  DevBuf d_bytes_gather;  // ykpred_comm_allgather_bytes
+  DevBuf d_topo_agree;  // node-sharded: the shape of every rank's topology histograms (agree_topology)
+  u64 dict_digest = 0;  // ykpred_set_dictionary_digest
   // fused rows (k_fused_rows): the zone-B classes no run kernel takes whose rows are plain plane rows, resolved to records at class-build time
   int fuse_rows = 1;                 // tunable (YKPRED_TUNE fuse_rows): 0 = those classes stay with the chunk writers
   int fuse_wpl = 0;                  // tunable (YKPRED_TUNE fuse_wpl): words per lane of k_fused_rows (1, 2, 5); 0 = from the row width
@@ -1491,10 +1494,53 @@ Rccl* rccl() {
     if (_s != ncclSuccess) return fail(e, YKPRED_E_DEVICE, std::string(#call) + ": " + rccl()->GetErrorString(_s)); \
   } while (0)
 
+// What the sum needs the ranks to agree on: the same constraints over the same per-key domain counts, so that cell c is the
+// same (constraint, domain) on every rank, and the same dictionaries behind the ids (ykpred_set_dictionary_digest: the host
+// makes them cluster-wide at ykhost_comm_init; a later node or pod update can still bring a value or class to one shard only).
+u64 topology_digest(const ykpred_engine* e) {
+  u64 h = 0xcbf29ce484222325ull;
+  auto mix = [&](u64 v) { h = (h ^ v) * 0x100000001b3ull; };
+  mix((u64)e->spread_cells);
+  mix((u64)e->spread_constraints);
+  mix((u64)e->KD);
+  mix((u64)e->KS);
+  for (int32_t d : e->h_domain_sizes) mix((u64)(uint32_t)d);
+  mix(e->dict_digest);  // (the host's digest of WHAT the ids stand for: key strings, domain values, selector classes)
+  return h;
+}
+struct TopoShape {
+  int64_t cells;
+  u64 digest;
+};
+// Every rank learns every rank's histogram shape; a mismatch is the SAME error on every rank, before anybody sums cells that do
+// not line up (or indexes a peer's histogram with its delta records) and before anybody leaves a collective the others enter.
+int agree_topology(ykpred_engine* e, hipStream_t st, const char* where) {
+  const int W = e->comm_world;
+  const TopoShape mine{e->spread_cells, topology_digest(e)};
+  HIPCHK(e->d_topo_agree.ensure((size_t)(W + 1) * sizeof(TopoShape)));
+  TopoShape* d = e->d_topo_agree.as<TopoShape>();
+  HIPCHK(hipMemcpyAsync(d + W, &mine, sizeof mine, hipMemcpyHostToDevice, st));
+  NCCLCHK(rccl()->AllGather(d + W, d, sizeof(TopoShape), ncclInt8, e->comm, st));
+  std::vector<TopoShape> all((size_t)W);
+  HIPCHK(hipMemcpyAsync(all.data(), d, (size_t)W * sizeof(TopoShape), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  // (YKPRED_E_INVALID, not _STATE: a host answers _STATE with a full evaluation, another collective the others would not enter)
+  for (int g = 0; g < W; ++g)
+    if (all[(size_t)g].cells != all[0].cells || all[(size_t)g].digest != all[0].digest)
+      return fail(e, YKPRED_E_INVALID, std::string(where) + " (sharded): rank " + std::to_string(g) + "'s topology histograms have " +
+                                         std::to_string(all[(size_t)g].cells) + " cells, rank 0's " + std::to_string(all[0].cells) +
+                                         (all[(size_t)g].cells == all[0].cells ? " laid out differently" : "") +
+                                         ": the shards do not share the topology-domain dictionaries (a node update brought a domain to one "
+                                         "shard only?) — no rank sums them");
+  return YKPRED_OK;
+}
+
 // Cluster-wide PreFilter state of the topology plugins on a node-sharded cluster: matches per (constraint, domain) add up,
 // "an eligible node carries the domain" is an OR (MAX of 0/1). Two small all-reduces (KBs) between count and min.
 int allreduce_spread(ykpred_engine* e, hipStream_t st) {
-  if (!e->comm || e->comm_world <= 1 || e->spread_cells == 0) return YKPRED_OK;
+  if (!e->comm || e->comm_world <= 1) return YKPRED_OK;
+  TRY(agree_topology(e, st, "topology histogram sum"));
+  if (e->spread_cells == 0) return YKPRED_OK;
   NCCLCHK(rccl()->AllReduce(e->d_sp_cnt.p, e->d_sp_cnt.p, (size_t)e->spread_cells, ncclInt32, ncclSum, e->comm, st));
   NCCLCHK(rccl()->AllReduce(e->d_sp_present.p, e->d_sp_present.p, (size_t)e->spread_cells, ncclInt32, ncclMax, e->comm, st));
   return YKPRED_OK;
@@ -1707,7 +1753,7 @@ void ykpred_destroy(ykpred_engine_t* e) {
                     &e->d_rank, &e->d_perm, &e->d_sreq, &e->d_stol, &e->d_sflags, &e->d_aff_off, &e->d_aff_terms, &e->d_pre_off,
                     &e->d_pre_terms, &e->d_dim_val, &e->d_dim_order, &e->d_dim_chunk_dim, &e->d_dim_chunk_begin, &e->d_dim_chunk_len,
                     &e->d_res_rows, &e->d_big_dim, &e->d_walk_big, &e->d_walk_begin, &e->d_walk_len, &e->d_sfree_c, &e->d_pmask_c,
-                    &e->d_sfree_r, &e->d_pmask_r, &e->d_rbits_c, &e->d_sorted, &e->d_sorted_off, &e->d_ent_c, &e->d_agree, &e->d_fuse_rec, &e->d_fuse_combo_rec, &e->d_fuse_combo, &e->d_run_ranges, &e->d_no_decide, &e->d_glin_r, &e->d_run_classes, &e->d_run_units, &e->d_sweep_rows, &e->d_sweep_runs, &e->d_sweep_units, &e->d_chunk_list_b0, &e->d_walk2_order, &e->d_walk2_big, &e->d_walk2_begin, &e->d_walk2_len, &e->d_idx_c, &e->d_win_r, &e->d_pfx_r, &e->d_slice_desc, &e->d_slice_general, &e->d_chunk_list_b, &e->d_first_r, &e->d_sig_tol, &e->d_sig_tolflags, &e->d_sig_aff_flags, &e->d_sig_aff_off,
+                    &e->d_sfree_r, &e->d_pmask_r, &e->d_rbits_c, &e->d_sorted, &e->d_sorted_off, &e->d_ent_c, &e->d_agree, &e->d_topo_agree, &e->d_bytes_gather, &e->d_fuse_rec, &e->d_fuse_combo_rec, &e->d_fuse_combo, &e->d_run_ranges, &e->d_no_decide, &e->d_glin_r, &e->d_run_classes, &e->d_run_units, &e->d_sweep_rows, &e->d_sweep_runs, &e->d_sweep_units, &e->d_chunk_list_b0, &e->d_walk2_order, &e->d_walk2_big, &e->d_walk2_begin, &e->d_walk2_len, &e->d_idx_c, &e->d_win_r, &e->d_pfx_r, &e->d_slice_desc, &e->d_slice_general, &e->d_chunk_list_b, &e->d_first_r, &e->d_sig_tol, &e->d_sig_tolflags, &e->d_sig_aff_flags, &e->d_sig_aff_off,
                     &e->d_sig_aff_terms, &e->d_sig_pre_off, &e->d_sig_pre_terms, &e->d_pod_spec, &e->d_pod_pin, &e->d_pod_class,
                     &e->d_class_sig, &e->d_class_pin, &e->d_class_first, &e->d_class_word, &e->d_chunk_class, &e->d_chunk_begin, &e->d_chunk_len, &e->d_chunk_first,
                     &e->d_pod_row, &e->d_band_tab, &e->d_class_rows_a, &e->d_class_list_a, &e->d_class_slot_a, &e->d_fix_row, &e->d_fix_slot, &e->d_chunk_zone,
@@ -3398,15 +3444,28 @@ int32_t ykpred_allocate_round(ykpred_engine_t* e, uint32_t pre, uint32_t filt, i
   const bool sharded = e->comm && e->comm_world > 1;
   const bool stale = e->classes_dirty || !e->last_eval_valid || !e->rank_valid || e->bitmap_epoch != e->nodes_epoch || pre != e->last_pre || filt != e->last_filt ||
                      e->ranked_pre != pre || e->ranked_filt != filt || e->ranked_nodes_epoch != e->nodes_epoch || e->ranked_specs_version != e->specs_version;
+  const bool fx_current = e->fx_version == e->specs_version;
+  const bool topo_on = (pre & filt & (YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD | YKPRED_PLUGIN_INTER_POD_AFFINITY)) && e->fam_spread.D > 0;
+  const bool ports_on = (pre & filt & YKPRED_PLUGIN_NODE_PORTS) && e->KP > 0;
+  bool port_asks = false;  // some ask of the round requests a host port: the round keeps the nodes' port words live
+  for (int i = 0; i < n_asks && ports_on && !port_asks; ++i) {
+    if (asks[i] < 0 || asks[i] >= e->P) break;  // (refused below)
+    const size_t sp = (size_t)e->h_pod_spec[(size_t)asks[i]];
+    for (int k = 0; k < e->KP; ++k) port_asks = port_asks || e->h_wanted[sp * (size_t)e->KP + (size_t)k] != 0;
+  }
   if (sharded) {
     // The sharded round is collective: a rank that left through a rank-local exit (no current evaluation, a patched ask, a list that
     // differs from the other ranks' — per-shard dictionaries can route different asks away) would leave the others blocked in the
     // first all-gather. So the ranks AGREE first — status, ask count, a hash of the list — and all of them return the same error.
+    // The histogram shape is part of it: the delta records of an owner's assumes index every other rank's histograms.
     struct Agree {
       int32_t rc, n;
       u64 hash;
+      int64_t cells;
+      u64 topo;
     };
-    Agree mine{stale ? YKPRED_E_STATE : YKPRED_OK, n_asks, 0x9e3779b97f4a7c15ull};
+    Agree mine{stale ? YKPRED_E_STATE : YKPRED_OK, n_asks, 0x9e3779b97f4a7c15ull, topo_on ? e->spread_cells : 0, topo_on ? topology_digest(e) : 0};
+    if (mine.rc == YKPRED_OK && (topo_on || port_asks) && !fx_current) mine.rc = YKPRED_E_UNSUPPORTED;
     for (int i = 0; i < n_asks; ++i) {
       mine.hash = (mine.hash ^ (u64)(uint32_t)asks[i]) * 0x100000001b3ull;
       if (asks[i] < 0 || asks[i] >= e->P) mine.rc = YKPRED_E_INVALID;
@@ -3421,31 +3480,32 @@ int32_t ykpred_allocate_round(ykpred_engine_t* e, uint32_t pre, uint32_t filt, i
     std::vector<Agree> all((size_t)W);
     HIPCHK(hipMemcpyAsync(all.data(), d, (size_t)W * sizeof(Agree), hipMemcpyDeviceToHost, e->own_stream));
     HIPCHK(hipStreamSynchronize(e->own_stream));
+    // (one verdict from all[] alone, in a fixed order — status, histogram shape, ask list — so every rank returns the same code)
     for (int g = 0; g < W; ++g) {
       if (all[(size_t)g].rc != YKPRED_OK)
         return fail(e, all[(size_t)g].rc, "allocate_round (sharded): rank " + std::to_string(g) + " cannot run the round (no current evaluation with decisions, "
-                                          "an ask patched and not re-evaluated, or an ask index out of range): no rank runs it");
-      if (all[(size_t)g].n != mine.n || all[(size_t)g].hash != mine.hash)
+                                          "an ask patched and not re-evaluated, an ask index out of range, or topology constraints / host ports "
+                                          "without the specs' effects uploaded): no rank runs it");
+    }
+    for (int g = 0; g < W; ++g)
+      if (all[(size_t)g].cells != all[0].cells || all[(size_t)g].topo != all[0].topo)
+        return fail(e, YKPRED_E_INVALID, "allocate_round (sharded): rank " + std::to_string(g) + "'s topology histograms are laid out differently from rank 0's (" +
+                                             std::to_string(all[(size_t)g].cells) + " against " + std::to_string(all[0].cells) +
+                                             " cells, or other dictionaries behind the ids): the shards do not share the topology-domain dictionaries — no rank runs the round");
+    for (int g = 0; g < W; ++g) {
+      if (all[(size_t)g].n != all[0].n || all[(size_t)g].hash != all[0].hash)
         return fail(e, YKPRED_E_INVALID, "allocate_round (sharded): rank " + std::to_string(g) + " was handed a different ask list: every rank passes the same asks in the same order");
     }
   }
   if (stale)
     return fail(e, YKPRED_E_STATE, "allocate_round: no current evaluation WITH decisions of these plugin lists (run ykpred_eval with YKPRED_OUT_DECISIONS)");
-  const bool fx_current = e->fx_version == e->specs_version;
-  const bool topo_on = (pre & filt & (YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD | YKPRED_PLUGIN_INTER_POD_AFFINITY)) && e->fam_spread.D > 0;
   if (topo_on && !fx_current)
     return fail(e, YKPRED_E_UNSUPPORTED, "allocate_round: topology constraints are active (an assumed pod's labels move the histograms of later asks) and the "
                                          "specs' effects are not uploaded (ykpred_set_spec_effects): decide ask by ask");
-  const bool ports_on = (pre & filt & YKPRED_PLUGIN_NODE_PORTS) && e->KP > 0;
-  bool port_asks = false;  // some ask of the round requests a host port: the round keeps the nodes' port words live
   for (int i = 0; i < n_asks; ++i) {
     if (asks[i] < 0 || asks[i] >= e->P) return fail(e, YKPRED_E_INVALID, "allocate_round: ask index out of range");
     if ((size_t)asks[i] < e->h_row_stale.size() && e->h_row_stale[(size_t)asks[i]])
       return fail(e, YKPRED_E_STATE, "allocate_round: an ask of the round was patched and not re-evaluated yet");
-    if (ports_on && !port_asks) {
-      const size_t sp = (size_t)e->h_pod_spec[(size_t)asks[i]];
-      for (int k = 0; k < e->KP; ++k) port_asks = port_asks || e->h_wanted[sp * (size_t)e->KP + (size_t)k] != 0;
-    }
   }
   if (port_asks && !fx_current)
     return fail(e, YKPRED_E_UNSUPPORTED, "allocate_round: an ask of the round requests a host port (an assumed pod's ports change later answers) and the specs' "
@@ -3623,8 +3683,9 @@ int32_t ykpred_allocate_round(ykpred_engine_t* e, uint32_t pre, uint32_t filt, i
     //      signature), an ask with a topology signature behind an accepted contribution to the histograms. Runs of one spec are
     //      accepted at once (k_allocate_round's run argument);
     //   4. the owners of the accepted nodes assume them (k_allocate_round, assume mode), everybody moves on behind the prefix.
-    // The decisions equal the sequential loop's; across shards the tie-break between equal keys is the cluster-wide node index (as in
-    // ykpred_exchange_decisions: NodeID order wherever names are zero-padded), on one GPU the NodeID rank itself.
+    // The decisions equal the sequential loop's; the tie-break between equal keys is (shard, NodeID rank inside the shard): the shards
+    // are ranges of the name-sorted node list, so that is NodeID order across the cluster whatever order each shard's nodes were
+    // inserted in (the cluster-wide node index is not). On one GPU it is the NodeID rank itself.
     Rccl* r = sharded ? rccl() : nullptr;
     const int W = sharded ? e->comm_world : 1, me = sharded ? e->comm_rank : 0;
     constexpr int K = ykk::kPropK;
@@ -3673,7 +3734,7 @@ int32_t ykpred_allocate_round(ykpred_engine_t* e, uint32_t pre, uint32_t filt, i
       return false;
     };
     struct Accepted {
-      int64_t ord;     // the tie-break between equal keys: cluster-wide node index (world > 1) / NodeID rank (one GPU)
+      int64_t ord;     // the tie-break between equal keys: (shard << 32) | NodeID rank inside it (world > 1) / NodeID rank (one GPU)
       int64_t gnode;   // cluster-wide node index
       u64 key0, key1;  // the node's key when it was proposed / after the accepted pods
       i64 alloc[ykk::kMaxR], used[ykk::kMaxR];  // its resource columns after the accepted pods
@@ -3748,7 +3809,9 @@ int32_t ykpred_allocate_round(ykpred_engine_t* e, uint32_t pre, uint32_t filt, i
         const u64* cross = (const u64*)(all + (size_t)a2.rank * nbytes + (size_t)b * K * sizeof(ykk::RoundProposal));
         return a2.didx >= 0 && ((cross[(size_t)m * (size_t)cw + (size_t)(a2.didx >> 6)] >> (a2.didx & 63)) & 1ull) != 0;
       };
-      auto ord_of = [&](const ykk::RoundProposal& p) { return W > 1 ? (int64_t)p.gnode : (int64_t)p.pad; };
+      // (shard, NodeID rank inside it): the shards are ranges of the name-sorted node list, so that is the cluster's NodeID order
+      // whatever order a shard's nodes were inserted in — the cluster-wide index is not
+      auto ord_of = [&](int g, const ykk::RoundProposal& p) { return W > 1 ? (((int64_t)g << 32) | (int64_t)(uint32_t)p.pad) : (int64_t)p.pad; };
       acc.clear();
       acc_of.clear();
       forced.assign((size_t)b, -1);
@@ -3776,7 +3839,7 @@ int32_t ykpred_allocate_round(ykpred_engine_t* e, uint32_t pre, uint32_t filt, i
           for (int q = 0; q < K; ++q) {
             const ykk::RoundProposal& p = prop_of(g, m, q);
             if (p.node < 0) break;
-            ents.push_back(Entry{p.key, ord_of(p), g, q});
+            ents.push_back(Entry{p.key, ord_of(g, p), g, q});
             ++n;
           }
           if (n == K) {
@@ -4466,6 +4529,52 @@ int32_t ykpred_comm_init(ykpred_engine_t* e, const uint8_t* id, int32_t rank, in
   e->comm_world = world;
   e->node_offset = node_offset;
   e->hist_epoch = 0;  // shard-local histograms are not the cluster's
+  return YKPRED_OK;
+}
+
+int32_t ykpred_comm_allgather_bytes(ykpred_engine_t* e, const void* send, int64_t bytes, void* recv) {
+  YK_SERIALISE(e);
+  if (!e || bytes < 0 || (bytes > 0 && (!send || !recv))) return fail(e, YKPRED_E_INVALID, "comm_allgather_bytes: bad argument");
+  if (!e->comm) return fail(e, YKPRED_E_STATE, "comm_allgather_bytes: no communicator (ykpred_comm_init)");
+  HIPCHK(hipSetDevice(e->cfg.device));
+  const size_t W = (size_t)e->comm_world, n = (size_t)bytes;
+  // (one buffer: [world] receive slabs, then the send slab; at least a byte each, so that the collective always runs)
+  const size_t slab = std::max<size_t>(n, 1);
+  HIPCHK(e->d_bytes_gather.ensure((W + 1) * slab));
+  char* d = (char*)e->d_bytes_gather.p;
+  if (n) HIPCHK(hipMemcpyAsync(d + W * slab, send, n, hipMemcpyHostToDevice, e->own_stream));
+  NCCLCHK(rccl()->AllGather(d + W * slab, d, slab, ncclInt8, e->comm, e->own_stream));
+  if (n)
+    for (size_t g = 0; g < W; ++g) HIPCHK(hipMemcpyAsync((char*)recv + g * n, d + g * slab, n, hipMemcpyDeviceToHost, e->own_stream));
+  HIPCHK(hipStreamSynchronize(e->own_stream));
+  return YKPRED_OK;
+}
+
+int32_t ykpred_comm_adopt(ykpred_engine_t* to, ykpred_engine_t* from) {
+  if (!to || !from || to == from) return fail(to, YKPRED_E_INVALID, "comm_adopt: bad argument");
+  YK_SERIALISE(to);
+  if (to->comm) return fail(to, YKPRED_E_STATE, "comm_adopt: a communicator is already attached");
+  if (!from->comm) return fail(to, YKPRED_E_STATE, "comm_adopt: the other engine carries no communicator");
+  if (to->cfg.device != from->cfg.device) return fail(to, YKPRED_E_INVALID, "comm_adopt: the engines live on different devices");
+  {
+    std::lock_guard<std::recursive_mutex> other(from->mu);
+    to->comm = from->comm;
+    to->comm_rank = from->comm_rank;
+    to->comm_world = from->comm_world;
+    to->node_offset = from->node_offset;
+    from->comm = nullptr;
+    from->comm_rank = 0;
+    from->comm_world = 1;
+    from->node_offset = 0;
+  }
+  to->hist_epoch = 0;
+  return YKPRED_OK;
+}
+
+int32_t ykpred_set_dictionary_digest(ykpred_engine_t* e, uint64_t digest) {
+  YK_SERIALISE(e);
+  if (!e) return YKPRED_E_INVALID;
+  e->dict_digest = digest;
   return YKPRED_OK;
 }
 

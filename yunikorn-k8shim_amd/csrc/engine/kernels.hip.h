@@ -3100,10 +3100,11 @@ struct RoundProposal {      // a shard's best node for an ask, and what the othe
   int fits;                 // how many pods of the ask's spec the node still holds when they couple through resources only, else 1
   i64 alloc[kMaxR], req[kMaxR];  // Allocatable and Requested of every resource dimension ([0], [1] = cpu, memory: the key after k more pods
                             // of a spec is arithmetic on these; all of them: whether a LATER ask of the batch still fits the node is too)
-  int gnode, room;          // node index in the whole cluster (the shard's node offset + node): the tie-break between equal keys;
+  int gnode, room;          // node index in the whole cluster (the shard's node offset + node): how the decisions name it;
                             // pod slots left (AllowedPodNumber - len(Pods))
   int didx, pad;            // batched rounds: the node's number among the distinct nodes its shard proposed in this batch (k_round_distinct);
-                            // pad = its NodeID rank inside the shard (the tie-break on one GPU)
+                            // pad = its NodeID rank inside the shard (the tie-break between equal keys: with the shard in front of it
+                            // across shards, alone on one GPU)
 };
 struct RoundArgs {
   int first, n_asks;        // this launch decides asks [first, first + n_asks) of the round

@@ -233,6 +233,33 @@ class Encoder {
   std::vector<HostPort> port_dict;                                    // requested host port k (NodePorts)
   std::vector<std::string> topo_keys;                                 // topology key k
   std::vector<std::unordered_map<std::string, int>> domain_ids;       // value → id, per key (ids follow sorted values)
+  // Values every rebuild numbers besides the nodes' own, per topology key: on a node-sharded cluster the other shards' values
+  // (ykhost_topology_merge), so that domain id d is the same value on every shard and the shards' histograms line up cell by cell.
+  std::map<std::string, std::set<std::string>> domain_floor;
+  // Templates of pods on OTHER shards' nodes that carry required anti-affinity terms (ykhost_topology_merge, in rank order): they
+  // are existing-anti templates of every rebuild like the shard's own, so the topology keys and count classes they register are
+  // numbered the same on every shard (a shard counts only its own pods into them).
+  std::vector<const PodTemplate*> anti_floor;
+
+  // What the topology ids stand for — key strings, each key's values in id order, the selector classes' keys in class order:
+  // equal on shards whose histograms line up cell by cell (ykpred_set_dictionary_digest).
+  uint64_t topology_dictionary_digest() const {
+    uint64_t h = 0xcbf29ce484222325ull;
+    auto mix = [&](const std::string& v) {
+      for (unsigned char c : v) h = (h ^ c) * 0x100000001b3ull;
+      h = (h ^ 0x1f) * 0x100000001b3ull;
+    };
+    for (size_t k = 0; k < topo_keys.size(); ++k) {
+      mix(topo_keys[k]);
+      std::vector<const std::string*> by_id(k < domain_ids.size() ? domain_ids[k].size() : 0, nullptr);
+      if (k < domain_ids.size())
+        for (auto& kv : domain_ids[k])
+          if (kv.second >= 0 && (size_t)kv.second < by_id.size()) by_id[(size_t)kv.second] = &kv.first;
+      for (const std::string* v : by_id) mix(v ? *v : std::string());
+    }
+    for (const std::string& key : sel_keys_) mix(key);
+    return h;
+  }
   std::vector<SelectorClass> sel_classes;                             // selector class s
   std::unordered_map<const PodTemplate*, std::string> unsupported;    // asks' templates the engine does not evaluate → why
   // engine limits (kernels.hip.h: kMaxR / kMaxKT / kMaxW / kMaxKP / kMaxKD; selector classes: ykpred_create)
@@ -298,7 +325,7 @@ class Encoder {
     // existing pod for every ask behind it (satisfyExistingPodsAntiAffinity). Their count classes exist from the start (all
     // zero until somebody is assumed), so a round never has to stop for a dictionary rebuild and the device can run it.
     existing_anti_templates_.clear();
-    if (may_have_existing_anti) {
+    if (may_have_existing_anti || !anti_floor.empty()) {
       std::set<const PodTemplate*> seen;
       auto consider = [&](const PodTemplate* tpl) {
         if (tpl->pod_anti_affinity.empty() || !seen.insert(tpl).second) return;
@@ -325,6 +352,7 @@ class Encoder {
       // template the engine cannot evaluate is never assumed by a device round: it stays out)
       for (const PodTemplate* t : templates)
         if (!t->pod_anti_affinity.empty() && template_error(*t).empty()) consider(t);
+      for (const PodTemplate* t : anti_floor) consider(t);  // (the cluster's, in rank order: the same numbering on every shard)
       for (const NodeInfo* ni : nodes)
         for (const Pod* p : ni->pods) consider(p->tpl);
     }
@@ -479,6 +507,8 @@ class Encoder {
         auto it = ni->node.labels.find(topo_keys[(size_t)k]);
         if (it != ni->node.labels.end()) values.insert(it->second);
       }
+      auto fl = domain_floor.find(topo_keys[(size_t)k]);
+      if (fl != domain_floor.end()) values.insert(fl->second.begin(), fl->second.end());
       int id = 0;
       for (auto& v : values) domain_ids[(size_t)k][v] = id++;
     }

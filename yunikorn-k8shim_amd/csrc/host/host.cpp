@@ -340,13 +340,16 @@ int recreate_engine(ykhost* h) {
   if (h->eng && h->cfgR == h->enc.R && h->cfgKT == h->enc.KT && h->cfgW == h->enc.W && h->cfgKD == h->enc.KD && h->cfgKS == h->enc.KS &&
       h->cfgKP == h->enc.KP)
     return 0;
-  if (h->eng && h->comm_attached)
-    return fail(h, "the dictionary shape changed on an engine that carries an RCCL communicator: the shard has to be re-created "
-                   "(ykhost_comm_init is collective and cannot be repeated silently)", YKPRED_E_STATE);
-  if (h->eng) ykpred_destroy(h->eng);
+  // (an engine that carries the communicator hands it to its successor: ykpred_comm_init cannot be repeated from one id)
+  ykpred_engine_t* old = h->eng;
   h->eng = nullptr;
+  if (old && !h->comm_attached) {
+    ykpred_destroy(old);
+    old = nullptr;
+  }
   h->fx_uploaded = false;
   if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
+  std::unique_ptr<ykpred_engine_t, void (*)(ykpred_engine_t*)> predecessor(old, ykpred_destroy);
   ykpred_config_t c{};
   c.abi_version = YKPRED_ABI_VERSION;
   c.device = h->device;
@@ -358,7 +361,17 @@ int recreate_engine(ykhost* h) {
   c.port_words = h->enc.KP;
   // (engine tunables for tests come from YKPRED_TUNE, read by ykpred_create itself)
   int r = ykpred_create(&c, &h->eng);
-  if (r != YKPRED_OK) return fail(h, std::string("ykpred_create: ") + ykpred_last_error(nullptr), r);
+  if (r != YKPRED_OK) {
+    h->comm_attached = false;  // (the predecessor goes, and its communicator with it)
+    return fail(h, std::string("ykpred_create: ") + ykpred_last_error(nullptr), r);
+  }
+  if (predecessor) {
+    r = ykpred_comm_adopt(h->eng, predecessor.get());
+    if (r != YKPRED_OK) {
+      h->comm_attached = false;
+      return fail(h, std::string("ykpred_comm_adopt: ") + ykpred_last_error(h->eng), r);
+    }
+  }
   h->cfgR = c.num_resources;
   h->cfgKT = c.taint_words;
   h->cfgW = c.label_words;
@@ -903,6 +916,7 @@ int full_sync(ykhost* h) {
   if (rc) return fail(h, std::string("ykpred_set_row_capacity: ") + ykpred_last_error(h->eng), rc);
   rc = ykpred_set_nodes(h->eng, &T.nt);
   if (rc) return fail(h, std::string("ykpred_set_nodes: ") + ykpred_last_error(h->eng), rc);
+  if (h->comm_attached) ykpred_set_dictionary_digest(h->eng, h->enc.topology_dictionary_digest());  // (compared before histograms are summed)
   h->fx_uploaded = false;
   rc = ykpred_set_specs(h->eng, &T.sp);
   if (rc) return fail(h, std::string("ykpred_set_specs: ") + ykpred_last_error(h->eng), rc);
@@ -2493,6 +2507,16 @@ int64_t ykhost_encoded_tables_json(ykhost_t* h, char* out, int64_t len) {
     ints("effect_count", fx_cnt.data(), fx_cnt.size());
     masks("occupied_ports", occupied.data(), S * KP);
   }
+  {
+    const std::vector<int32_t> ds = h->enc.domain_sizes();
+    ints("domain_sizes", ds.data(), ds.size());
+    o += "\"topology_keys\":[";
+    for (size_t k = 0; k < h->enc.topo_keys.size(); ++k) {
+      if (k) o.push_back(',');
+      js_str(o, h->enc.topo_keys[k]);
+    }
+    o += "],";
+  }
   o += "\"spread_constraints\":" + std::to_string(T.spread.size()) + "}";
   if (out && len > 0) copy_out(o, out, len);
   return (int64_t)o.size() + 1;
@@ -2516,6 +2540,112 @@ int32_t ykhost_set_row_capacity(ykhost_t* h, int32_t rows) {
   return 0;
 }
 
+// ---- node-sharded clusters: one topology-domain dictionary for all shards ------------------------------------------------
+// A shard numbers the values of a topology key from ITS nodes, and the count classes of existing anti-affinity terms from ITS
+// pods; the shards' histograms are summed cell by cell and a round's delta records index every shard's histograms with the
+// owner's ids, so the numbering has to be the cluster's. The blob is a shard's node-side share of the dictionaries: its first
+// and last NodeID, the templates of its pods with required anti-affinity terms, and the values per topology key.
+//   N \x1f <nodes> \x1f <first name> \x1f <last name> \n
+//   per template of its pods with required anti-affinity terms:   P \x1f <a pod document of that template> \n
+//   per topology key:   K \x1f <key> (\x1f <value>)* \n
+// (label keys, values and node names never hold control characters)
+}  // extern "C"
+static std::string topology_blob(ykhost* h) {
+  std::string o = "N\x1f" + std::to_string(h->nodes.size());
+  std::string lo, hi;
+  for (const NodeInfo* ni : h->nodes) {
+    if (lo.empty() || ni->node.name < lo) lo = ni->node.name;
+    if (hi.empty() || ni->node.name > hi) hi = ni->node.name;
+  }
+  o += "\x1f" + lo + "\x1f" + hi + "\n";
+  // the templates of this shard's pods that carry required anti-affinity terms, one pod document each (node order)
+  std::set<const PodTemplate*> seen;
+  for (const NodeInfo* ni : h->nodes)
+    for (const Pod* p : ni->pods)
+      if (p->tpl && !p->tpl->pod_anti_affinity.empty() && seen.insert(p->tpl).second) {
+        std::string doc;
+        pod_json(*p, doc);
+        for (char& ch : doc)
+          if (ch == '\n') ch = ' ';
+        o += "P\x1f" + doc + "\n";
+      }
+  for (size_t k = 0; k < h->enc.topo_keys.size(); ++k) {
+    std::vector<std::string> values;
+    for (auto& kv : h->enc.domain_ids[k]) values.push_back(kv.first);
+    std::sort(values.begin(), values.end());
+    o += "K\x1f" + h->enc.topo_keys[k];
+    for (auto& v : values) o += "\x1f" + v;
+    o += "\n";
+  }
+  return o;
+}
+static std::vector<std::string> split_on(const std::string& s, char sep) {
+  std::vector<std::string> out(1);
+  for (char c : s) {
+    if (c == sep) out.emplace_back();
+    else out.back().push_back(c);
+  }
+  return out;
+}
+extern "C" {
+
+int64_t ykhost_topology_export(ykhost_t* h, char* out, int64_t len) {
+  YKHOST_LOCKED(h);
+  if (h->eng) {
+    const int rc = sync(h);  // (a device handle: the dictionaries the engine holds, brought up to date)
+    if (rc) return rc;
+  } else {
+    // a mirror-only handle keeps no encoded state between calls: encode the current objects (like ykhost_encoded_tables_json)
+    EncodedTables T;
+    const int rc = encode_tables(h, &T);
+    h->dirty_all = true;
+    if (rc) return rc;
+  }
+  const std::string o = topology_blob(h);
+  if (out && len > 0) copy_out(o, out, len);
+  return (int64_t)o.size() + 1;
+}
+
+int32_t ykhost_topology_merge(ykhost_t* h, const char* blobs, int64_t len) {
+  YKHOST_LOCKED(h);
+  if (!blobs || len < 0) return fail(h, "topology_merge: bad argument");
+  const std::string all(blobs, (size_t)len);
+  // shards in rank order (blobs separated by NUL): the name-sorted contract — every NodeID of shard r sorts before every NodeID
+  // of shard r + 1 — is what makes (shard, NodeID rank inside it) the cluster's NodeID order (the tie-break of the decisions)
+  std::string prev_hi;
+  int prev_rank = -1, rank = 0;
+  bool grew = false;
+  for (const std::string& blob : split_on(all, '\0')) {
+    if (blob.empty()) continue;
+    for (const std::string& line : split_on(blob, '\n')) {
+      const std::vector<std::string> f = split_on(line, '\x1f');
+      if (f[0] == "N" && f.size() == 4) {
+        if (f[1] != "0") {
+          if (prev_rank >= 0 && !(prev_hi < f[2]))
+            return fail(h, "topology_merge: the shards are not ranges of the name-sorted node list (shard " + std::to_string(prev_rank) + " ends with '" +
+                               prev_hi + "', shard " + std::to_string(rank) + " starts with '" + f[2] + "')", YKPRED_E_INVALID);
+          prev_hi = f[3];
+          prev_rank = rank;
+        }
+      } else if (f[0] == "P" && line.size() > 2) {
+        mj::ValuePtr v = mj::parse(line.substr(2));
+        if (!v) return fail(h, "topology_merge: a pod document of shard " + std::to_string(rank) + " does not parse", YKPRED_E_INVALID);
+        const PodTemplate* t = h->pool.intern(read_template(*v));
+        if (std::find(h->enc.anti_floor.begin(), h->enc.anti_floor.end(), t) == h->enc.anti_floor.end()) {
+          h->enc.anti_floor.push_back(t);
+          grew = true;
+        }
+      } else if (f[0] == "K" && f.size() >= 2) {
+        std::set<std::string>& floor = h->enc.domain_floor[f[1]];
+        for (size_t i = 2; i < f.size(); ++i) grew = floor.insert(f[i]).second || grew;
+      }
+    }
+    ++rank;
+  }
+  if (grew) h->dirty_all = true;  // the next sync numbers the union
+  return 0;
+}
+
 int32_t ykhost_comm_init(ykhost_t* h, const uint8_t* id, int32_t rank, int32_t world, int32_t node_offset) {
   YKHOST_LOCKED(h);
   int rc = sync(h);  // the engine of the final dictionary shape must exist before the communicator is attached to it
@@ -2523,7 +2653,27 @@ int32_t ykhost_comm_init(ykhost_t* h, const uint8_t* id, int32_t rank, int32_t w
   rc = ykpred_comm_init(h->eng, id, rank, world, node_offset);
   if (rc) return fail(h, std::string("ykpred_comm_init: ") + ykpred_last_error(h->eng), rc);
   h->comm_attached = true;
-  return 0;
+  if (world <= 1) return 0;
+  // Every shard's node-side dictionary entries, to every shard (lengths first, then the blobs padded to the longest); each
+  // shard keeps the union as the floor of every later re-encode. Every rank merges the same blobs: the same verdict everywhere.
+  const std::string mine = topology_blob(h);
+  std::vector<int64_t> lens((size_t)world);
+  const int64_t my_len = (int64_t)mine.size();
+  rc = ykpred_comm_allgather_bytes(h->eng, &my_len, sizeof my_len, lens.data());
+  if (rc) return fail(h, std::string("ykpred_comm_allgather_bytes: ") + ykpred_last_error(h->eng), rc);
+  const int64_t longest = *std::max_element(lens.begin(), lens.end()) + 1;
+  std::string send(mine);
+  send.resize((size_t)longest, '\0');
+  std::string recv((size_t)(longest * world), '\0');
+  rc = ykpred_comm_allgather_bytes(h->eng, send.data(), longest, &recv[0]);
+  if (rc) return fail(h, std::string("ykpred_comm_allgather_bytes: ") + ykpred_last_error(h->eng), rc);
+  std::string blobs;
+  for (int g = 0; g < world; ++g) blobs += recv.substr((size_t)(g * longest), (size_t)lens[(size_t)g]) + '\0';
+  rc = ykhost_topology_merge(h, blobs.data(), (int64_t)blobs.size());
+  if (rc) return rc;
+  rc = sync(h);  // (the union re-numbers; classes from other shards' pods can change the shape: the new engine adopts the communicator)
+  if (rc) return rc;
+  return ykpred_set_dictionary_digest(h->eng, h->enc.topology_dictionary_digest());
 }
 
 int32_t ykhost_comm_destroy(ykhost_t* h) {

@@ -435,6 +435,19 @@ class GpuPredicateManager:
         buf = (C.c_uint8 * 128).from_buffer_copy(unique_id)
         self._check(self._L.ykhost_comm_init(self._h, buf, rank, world, node_offset))
 
+    def topology_export(self):
+        """This shard's node-side share of the topology-domain dictionaries (ykhost_topology_export): bytes. Needs no device."""
+        need = self._check(self._L.ykhost_topology_export(self._h, None, 0))
+        buf = C.create_string_buffer(need)
+        self._check(self._L.ykhost_topology_export(self._h, buf, need))
+        return buf.value
+
+    def topology_merge(self, exports):
+        """Every shard's export in rank order: the union becomes the floor of this handle's dictionaries (ykhost_topology_merge).
+        ykhost_comm_init does both halves itself over the communicator."""
+        blob = b"".join(x + b"\0" for x in exports)
+        self._check(self._L.ykhost_topology_merge(self._h, blob, len(blob)))
+
     def comm_destroy(self):
         self._check(self._L.ykhost_comm_destroy(self._h))
 
