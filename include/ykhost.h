@@ -220,6 +220,27 @@ int32_t ykhost_resident_stats(ykhost_t* h, int64_t* out5);
 int32_t ykhost_allocate_round(ykhost_t* h, int32_t n, const int32_t* asks, int32_t apply, int32_t* out_nodes /* [n] */);
 int32_t ykhost_round_stats(ykhost_t* h, int64_t* out4);
 
+/* WHY an ask fits nowhere (ykpred.h: ykpred_explain) — the text kube-scheduler prints for an unschedulable pod and the shim can put
+ * into the Message of the PodScheduled=False / Unschedulable condition (/root/reference/pkg/cache/context.go:1272-1285).
+ *   ykhost_explain          syncs, picks the phase's plugin lists and makes ONE engine call for the listed asks (NULL = asks 0..n-1):
+ *                           out_bins[i] = the YKPRED_EXPLAIN_BINS histogram of ask i over all nodes. An ask routed to the CPU manager
+ *                           gets [10] = N without a device call. A mirror-only handle fails like every other evaluation. On a
+ *                           node-sharded handle the call is collective and the bins are cluster-wide.
+ *   ykhost_explain_format   a PURE function of the bins and the handle's resource names (works on a mirror-only handle):
+ *                           total = bins[0] + ... + bins[10]; total == 0 gives "no nodes available to schedule pods"; otherwise
+ *                           "<bins[9]>/<total> nodes are available" + ": <count> <text>, <count> <text>." (or just "." without entries) —
+ *                           one entry per reason text with a count > 0, entries of equal text merged, the entry strings sorted
+ *                           bytewise ("10 x" before "2 y", as upstream sorts them). The wording is kube-scheduler's FitError (upstream
+ *                           wording, not reference-held); the texts are those of the per-pair messages. The taint entry is the generic
+ *                           "node(s) had untolerated taint": upstream's per-taint {key: value} breakdown is out of scope.
+ *                           → required length incl. NUL; writes at most `len` bytes.
+ *   ykhost_explain_message  explain + format for one ask by allocation key (pod UID). → required length, or
+ *                           YKHOST_E_POD_NOT_FOUND / YKHOST_E_NOT_AN_ASK as ykhost_is_pod_fit_node, YKHOST_E_UNSUPPORTED with the
+ *                           routing reason in `out` for an ask the engine does not evaluate. */
+int32_t ykhost_explain(ykhost_t* h, int32_t n, const int32_t* asks /* NULL = asks 0..n-1 */, int32_t allocate, int32_t* out_bins /* [n][32] */);
+int64_t ykhost_explain_format(ykhost_t* h, const int32_t* bins /* [32] */, char* out, int64_t len);
+int64_t ykhost_explain_message(ykhost_t* h, const char* allocation_key, int32_t allocate, char* out, int64_t len);
+
 /* Engine calls that came back YKPRED_E_DEVICE / YKPRED_E_NOMEM so far (failed allocation, lost device). Each one marks the whole
  * device state stale: the failing call returns its error (Predicates() < 0: the Go manager routes the ask to the CPU predicate
  * manager — SURVEY.md §5, "must degrade, never fail scheduling"), the mirror stays intact, and the next ykhost_sync /

@@ -38,7 +38,9 @@
 extern "C" {
 #endif
 
-/* 4: ykpred_set_spec_effects + ykpred_spec_effects_t, ykpred_comm_info (round 5 added them without a bump: a host built against the
+/* (ykpred_explain + YKPRED_EXPLAIN_BINS arrived WITHIN version 4, without a bump: a host that needs the call detects it by the
+ *    exported symbol — dlsym("ykpred_explain") — not by the version number)
+ * 4: ykpred_set_spec_effects + ykpred_spec_effects_t, ykpred_comm_info (round 5 added them without a bump: a host built against the
  *    header could not tell an older library apart), ykpred_layout_t.sweep_rows / index_rows_walked / run_rows / fused_rows, ykpred_get_round_info
  * 3: ykpred_eval_args_t.bitmap_rows (a caller-owned bitmap states its size), ykpred_peek_row (the resident
  *    answer served to single Predicates() callbacks), ykpred_eval_nodes is collective on a sharded engine with topology signatures
@@ -428,6 +430,39 @@ int32_t ykpred_query_pod(ykpred_engine_t* e, int32_t pod_index, uint32_t prefilt
 /* ykpred_query_pod with one 4-byte word per node and a single device → host copy: bits 0-7 plugin code, bit 8 fit, bits 9-12
  * reason bits 0-3, bits 13.. the insufficient-resource bits (reason >> YKPRED_REASON_RESOURCE_SHIFT). */
 int32_t ykpred_query_pod_packed(ykpred_engine_t* e, int32_t pod_index, uint32_t prefilter_plugins, uint32_t filter_plugins, uint32_t* out /* [N] */);
+
+/* WHY an ask fits nowhere: for every listed ask the histogram of its Predicates() verdicts over ALL nodes of the table — what the
+ * default scheduler prints as "0/5000 nodes are available: 3100 Insufficient cpu, 1200 node(s) had untolerated taint, ..." and the
+ * shim can put into the Message of the PodScheduled=False / Unschedulable condition (/root/reference/pkg/cache/context.go:1272-1285).
+ * A reduction on the device: 32 integers per ask come back instead of 4 bytes x N per ask (ykpred_query_pod_packed + a host loop). */
+#define YKPRED_EXPLAIN_BINS 32
+/* per ask, int32[32], over all nodes of the table:
+ *  [0..8]   nodes whose FIRST failing plugin code is 0..8 (YKPRED_CODE_*; 0 = a PreFilter plugin rejected the pod)
+ *  [9]      nodes the ask fits
+ *  [10]     nodes not evaluated because the ask's spec is YKPRED_SPEC_UNSUPPORTED (then [10] == N and every other bin is 0)
+ *  [11]     0
+ *  [12..15] nodes whose verdict carries reason bit 0..3 (TOO_MANY_PODS, PREFILTER_NODE_NOT_ELIGIBLE, PREFILTER_REJECTED,
+ *           MISSING_TOPOLOGY_LABEL)
+ *  [16..23] nodes whose verdict carries "insufficient resource r", r = 0..7 (reason bit YKPRED_REASON_RESOURCE_SHIFT + r)
+ *  [24..31] 0
+ * Invariant: [0] + ... + [10] == N. A node with several reason bits counts in each of their bins.
+ * Source of the verdicts: for every listed ask and every node the contribution is exactly what ykpred_query returns for that pair
+ *   (fit, code, reason) — the kernel (k_explain) calls the same per-pair routine; no plugin rule is stated a second time.
+ * Evaluation state: the call reads the TABLES, not the bitmap. It needs no current evaluation and invalidates none:
+ *   ykpred_answer_state, the resident answer, the last bitmap and its checksum are the same after the call as before, and the
+ *   result is current right after a ykpred_update_node with no re-evaluation. With a topology plugin in both lists it prepares
+ *   the PodTopologySpread / InterPodAffinity histograms exactly as ykpred_query does.
+ * The listed asks are reduced to their distinct (spec, NodeName) tasks on the host; a row is copied to every ask of its task.
+ * Counts as one query (ykpred_get_counters out[3]); roctx range "ykpred:explain".
+ * Errors: YKPRED_E_INVALID for a bad pointer or an index out of range, YKPRED_E_STATE before the tables are uploaded; n_asks == 0
+ *   returns YKPRED_OK; a table of N == 0 nodes gives all-zero rows.
+ * NODE-SHARDED engines (communicator attached, world > 1): the call is COLLECTIVE — every rank passes the same asks — and every
+ *   rank returns CLUSTER-WIDE bins ([0..10] sum to the cluster's node count): the [tasks][32] table is summed with one all-reduce
+ *   (int32, SUM) before the copy to the host. Before it the ranks agree on (status, n_asks, the list) with one small all-gather, as
+ *   ykpred_allocate_round does: a rank that cannot run, or a differing list, makes every rank return the same error instead of
+ *   blocking in the reduce. */
+int32_t ykpred_explain(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks /* host, ask indices, any order, repeats allowed */,
+                       uint32_t prefilter_plugins, uint32_t filter_plugins, int32_t* out /* host, [n_asks][YKPRED_EXPLAIN_BINS] */);
 
 /* PreemptionPredicates (predicate_manager.go:141-179): victims are described by their request vectors, in order. */
 int32_t ykpred_preemption(ykpred_engine_t* e, int32_t pod_index, int32_t node_index, int32_t num_victims,

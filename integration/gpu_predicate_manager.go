@@ -411,6 +411,41 @@ func (m *gpuPredicateManager) Candidates(pod *v1.Pod, k int, allocate bool) ([]i
 	return out, true
 }
 
+// ExplainUnschedulable answers "why does this ask fit nowhere" with kube-scheduler's FitError text over ALL nodes — "0/5000 nodes
+// are available: 3100 Insufficient cpu, 1200 node(s) had untolerated taint." — reduced on the device (ykpred_explain: 32 integers per
+// ask cross the bus instead of one verdict per node). ONE crossing: ykhost_explain_message looks the ask up by allocation key, runs
+// the reduction with the phase's plugin lists and formats the line. Its place in the shim is the Message of the PodScheduled=False /
+// Unschedulable condition (context.go:1272-1285; INTEGRATION.md names the call site). ("", false) when the pod is not a mirrored ask,
+// is routed to the CPU predicate manager, or the engine failed: the caller keeps the message it has.
+func (m *gpuPredicateManager) ExplainUnschedulable(pod *v1.Pod, allocate bool) (string, bool) {
+	if pod == nil {
+		return "", false
+	}
+	alloc := C.int32_t(0)
+	if allocate {
+		alloc = 1
+	}
+	var message [2048]C.char
+	uid := C.CString(string(pod.UID))
+	rc := C.ykhost_explain_message(m.host, uid, alloc, &message[0], 2048)
+	C.free(unsafe.Pointer(uid))
+	switch {
+	case rc > 0:
+		return C.GoString(&message[0]), true
+	case rc == C.YKHOST_E_UNSUPPORTED:
+		m.Counters.RoutedUnsupported.Add(1)
+		return "", false
+	case rc == C.YKHOST_E_POD_NOT_FOUND || rc == C.YKHOST_E_NOT_AN_ASK:
+		m.Counters.RoutedNotMirrored.Add(1)
+		return "", false
+	default:
+		m.Counters.RoutedOnError.Add(1)
+		log.Log(log.ShimPredicates).Warn("GPU predicate engine error, no unschedulable summary for the ask",
+			zap.String("error", C.GoString(C.ykhost_last_error(m.host))))
+		return "", false
+	}
+}
+
 // ResidentStats: Predicates() calls answered from the mirrored resident answer, per pair because the node's column changed,
 // by whole-ask device queries, and the answer / failing-plugin fetches behind them.
 func (m *gpuPredicateManager) ResidentStats() (resident, dirtyColumn, query, answerFetches, codeFetches int64) {

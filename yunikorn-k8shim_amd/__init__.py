@@ -5,7 +5,7 @@ C++ stand-in for the Go shim side, include/ykhost.h) and thin ctypes bindings. S
 The package name contains a hyphen; import it with importlib.import_module("yunikorn-k8shim_amd").
 """
 from . import build  # noqa: F401
-from .predicate_manager import (ALL_PLUGINS, PLUGIN_BITS, GpuPredicateManager, PredicateError,  # noqa: F401
-                                UnsupportedAsk, plugin_mask)
+from .predicate_manager import (ALL_PLUGINS, EXPLAIN_BINS, EXPLAIN_FIT, EXPLAIN_REASON0, EXPLAIN_RESOURCE0,  # noqa: F401
+                                EXPLAIN_UNSUPPORTED, PLUGIN_BITS, GpuPredicateManager, PredicateError, UnsupportedAsk, plugin_mask)
 
 build_all = build.build_all

@@ -134,6 +134,7 @@ def load_ykpred():
     L.ykpred_pod_class.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
     L.ykpred_read_class_rows.argtypes = [C.c_void_p, C.c_void_p]
     L.ykpred_query_pod_packed.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.ykpred_explain.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     _pred = L
     return L
 
@@ -202,6 +203,11 @@ def load_ykhost():
     L.ykhost_resident_stats.argtypes = [C.c_void_p, C.c_void_p]
     L.ykhost_allocate_round.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     L.ykhost_round_stats.argtypes = [C.c_void_p, C.c_void_p]
+    L.ykhost_explain.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    L.ykhost_explain_format.restype = C.c_int64
+    L.ykhost_explain_format.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64]
+    L.ykhost_explain_message.restype = C.c_int64
+    L.ykhost_explain_message.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_char_p, C.c_int64]
     L.ykhost_device_errors.restype = C.c_int64
     L.ykhost_device_errors.argtypes = [C.c_void_p]
     _host = L

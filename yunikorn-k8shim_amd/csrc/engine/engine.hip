@@ -273,6 +273,7 @@ struct ykpred_engine {
   int sweep_rows[ykk::kMaxIdxRows] = {0, 0}, sweep_row_off[ykk::kMaxIdxRows + 1] = {0, 0, 0}, sweep_runs = 0;  // per walked dimension
   int index_rows_needed = 0;         // index rows some class OUTSIDE the sweep runs reads (the full pass walks only those)
   DevBuf d_agree;  // sharded rounds: what the ranks agree on before the first batch
+  DevBuf d_explain;  // ykpred_explain: task specs | task pins | [tasks][YKPRED_EXPLAIN_BINS] counts
   DevBuf d_bytes_gather;  // ykpred_comm_allgather_bytes
   DevBuf d_topo_agree;  // node-sharded: the shape of every rank's topology histograms (agree_topology)
   u64 dict_digest = 0;  // ykpred_set_dictionary_digest
@@ -4422,6 +4423,111 @@ int32_t ykpred_query_pod_packed(ykpred_engine_t* e, int32_t pod, uint32_t pre, u
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, e->d_scratch.p, N * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
+  return YKPRED_OK;
+}
+
+// Why an ask fits nowhere: the histogram of ykpred_query's verdicts over every node, reduced on the device (k_explain). Reads the
+// tables only — no bitmap, no evaluation state is consulted or changed.
+int32_t ykpred_explain(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, uint32_t pre, uint32_t filt, int32_t* out) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:explain");
+  if (e) e->n_queries++;
+  static_assert(ykk::kExplainBins == YKPRED_EXPLAIN_BINS, "k_explain writes the layout of ykpred.h");
+  constexpr size_t B = YKPRED_EXPLAIN_BINS;
+  if (!e) return YKPRED_E_INVALID;
+  const bool sharded = e->comm && e->comm_world > 1;
+  int rc = YKPRED_OK;
+  const char* why = "";
+  if (n_asks < 0 || (n_asks > 0 && (!asks || !out))) rc = YKPRED_E_INVALID, why = "explain: bad argument";
+  else if (!e->nodes_set || !e->specs_set || !e->pods_set) rc = YKPRED_E_STATE, why = "explain: tables not uploaded";
+  else
+    for (int i = 0; i < n_asks; ++i)
+      if (asks[i] < 0 || asks[i] >= e->P) rc = YKPRED_E_INVALID, why = "explain: index out of range";
+  if (!sharded && rc != YKPRED_OK) return fail(e, rc, why);
+  if (!sharded && n_asks == 0) return YKPRED_OK;
+  // Tasks: the distinct (spec, pin) of the list, numbered by first appearance; task_of[i] is ask i's row of the table. A sharded engine
+  // cannot key on the pin (a node index of ITS shard): an ask with a NodeName is a task of its own there, and with by_ask every
+  // distinct ask index is — the keys every rank derives alike whatever its own spec table merges.
+  std::vector<int32_t> task_of, t_spec, t_pin;
+  auto build_tasks = [&](bool by_ask) {
+    std::unordered_map<u64, int32_t> index;
+    task_of.assign((size_t)n_asks, 0);
+    t_spec.clear();
+    t_pin.clear();
+    for (int i = 0; i < n_asks; ++i) {
+      const int32_t a = asks[i], sp = e->h_pod_spec[(size_t)a], pin = e->h_pod_pin[(size_t)a];
+      u64 key = ((u64)(uint32_t)sp << 32) | (u64)(uint32_t)pin;
+      if (by_ask || (sharded && pin != YKPRED_NO_NODE_NAME)) key = (1ull << 63) | (u64)(uint32_t)a;
+      auto it = index.emplace(key, (int32_t)t_spec.size());
+      if (it.second) {
+        t_spec.push_back(sp);
+        t_pin.push_back(pin);
+      }
+      task_of[(size_t)i] = it.first->second;
+    }
+  };
+  if (rc == YKPRED_OK) build_tasks(false);
+  HIPCHK(hipSetDevice(e->cfg.device));
+  hipStream_t st = e->own_stream;
+  if (rc == YKPRED_OK && e->N > 0 && n_asks > 0) {
+    // (the histogram preparation of ykpred_query; on a sharded engine a stale histogram is a status the ranks agree on below)
+    if ((pre & filt & (YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD | YKPRED_PLUGIN_INTER_POD_AFFINITY))) rc = ensure_histograms(e, st);
+    else if (e->spread_dirty) rc = build_spread_tables(e, st);
+    if (rc != YKPRED_OK && !sharded) return rc;
+  }
+  if (sharded) {
+    // Collective: the ranks agree on (status, ask count, list, task partition) before anybody enters the reduce — a rank that cannot
+    // run, or a different list, is the SAME error on every rank. Partitions that differ (per-shard dictionaries merge specs
+    // differently) are no error: every rank then takes one task per distinct ask.
+    struct Agree {
+      int32_t rc, n;
+      u64 list, partition;
+    };
+    Agree mine{rc, n_asks, 0x9e3779b97f4a7c15ull, 0x9e3779b97f4a7c15ull};
+    if (rc == YKPRED_OK)
+      for (int i = 0; i < n_asks; ++i) {
+        mine.list = (mine.list ^ (u64)(uint32_t)asks[i]) * 0x100000001b3ull;
+        mine.partition = (mine.partition ^ (u64)(uint32_t)task_of[(size_t)i]) * 0x100000001b3ull;
+      }
+    const int W = e->comm_world;
+    HIPCHK(e->d_agree.ensure((size_t)(W + 1) * sizeof(Agree)));
+    Agree* d = e->d_agree.as<Agree>();
+    HIPCHK(hipMemcpyAsync(d + W, &mine, sizeof(Agree), hipMemcpyHostToDevice, st));
+    NCCLCHK(rccl()->AllGather(d + W, d, sizeof(Agree), ncclInt8, e->comm, st));
+    std::vector<Agree> all((size_t)W);
+    HIPCHK(hipMemcpyAsync(all.data(), d, (size_t)W * sizeof(Agree), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int g = 0; g < W; ++g)
+      if (all[(size_t)g].rc != YKPRED_OK)
+        return fail(e, all[(size_t)g].rc, "explain (sharded): rank " + std::to_string(g) + " cannot run the call (" +
+                                              (g == e->comm_rank && *why ? why : "bad argument, tables not uploaded, an index out of range or stale topology histograms") +
+                                              "): no rank runs it");
+    for (int g = 0; g < W; ++g)
+      if (all[(size_t)g].n != all[0].n || all[(size_t)g].list != all[0].list)
+        return fail(e, YKPRED_E_INVALID, "explain (sharded): rank " + std::to_string(g) + " was handed a different ask list: every rank passes the same asks");
+    if (n_asks == 0) return YKPRED_OK;
+    bool same = true;
+    for (int g = 0; g < W; ++g) same = same && all[(size_t)g].partition == all[0].partition;
+    if (!same) build_tasks(true);
+  }
+  const size_t T = t_spec.size();
+  HIPCHK(e->d_explain.ensure(T * (2 * sizeof(int32_t) + B * sizeof(int32_t)) + 64));
+  int32_t* d_bins = e->d_explain.as<int32_t>();  // (the table first: what the reduce and the copy move)
+  int32_t* d_spec = d_bins + T * B;
+  int32_t* d_pin = d_spec + T;
+  HIPCHK(hipMemsetAsync(d_bins, 0, T * B * sizeof(int32_t), st));
+  if (e->N > 0) {
+    HIPCHK(hipMemcpyAsync(d_spec, t_spec.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_pin, t_pin.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    const dim3 grid((unsigned)((T + ykk::kExplainTasks - 1) / ykk::kExplainTasks), (unsigned)((e->N + ykk::kBlock - 1) / ykk::kBlock));
+    hipLaunchKernelGGL(ykk::k_explain, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e), (int)T, d_spec, d_pin, pre, filt, d_bins);
+    HIPCHK(hipGetLastError());
+  }
+  if (sharded) NCCLCHK(rccl()->AllReduce(d_bins, d_bins, T * B, ncclInt32, ncclSum, e->comm, st));
+  std::vector<int32_t> rows(T * B);
+  HIPCHK(hipMemcpyAsync(rows.data(), d_bins, T * B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int i = 0; i < n_asks; ++i) memcpy(out + (size_t)i * B, rows.data() + (size_t)task_of[(size_t)i] * B, B * sizeof(int32_t));
   return YKPRED_OK;
 }
 

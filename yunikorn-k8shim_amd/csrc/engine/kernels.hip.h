@@ -2886,6 +2886,64 @@ __global__ __launch_bounds__(kBlock) void k_direct(NodeTable t, SpecTable s, int
   if (p < n_pods) bitmap[(size_t)pod_row[p] * row_stride + w] = (w < row_words) ? keep : 0ull;
 }
 
+// ykpred_explain: per task (a distinct (spec, pin) of the listed asks) the histogram of eval_pair's verdicts over ALL nodes, the layout of
+// include/ykpred.h (YKPRED_EXPLAIN_BINS): [0..8] first failing plugin code, [9] fit, [10] not evaluated (code 255), [12..15] reason bits
+// 0..3, [16..23] insufficient resource r. Grid as k_direct: blockIdx.x = chunk of kExplainTasks tasks (the unbounded axis), blockIdx.y =
+// group of 4 node words, so ONE task is spread over N/256 workgroups and MANY tasks read a node's columns once per chunk. lane = node: the
+// wave keeps its 64 nodes' columns in registers and walks the chunk's tasks (task data wave-uniform). A bin's count over the wave is the
+// popcount of a ballot — wave-uniform — and lane b keeps bin b, so a task costs the wave one LDS add of 32 lanes; the block's waves meet
+// in LDS and the block adds its non-zero (task, bin) cells to the table, which the host zeroed on the stream. Integer adds: the result
+// does not depend on the order the blocks arrive in. Lanes past N evaluate nothing and are in no ballot.
+constexpr int kExplainBins = 32;
+constexpr int kExplainTasks = 32;
+__global__ __launch_bounds__(kBlock) void k_explain(NodeTable t, SpecTable s, int n_tasks, const int* __restrict__ task_spec,
+                                                    const int* __restrict__ task_pin, unsigned pre_mask, unsigned filt_mask,
+                                                    int* __restrict__ bins) {
+  __shared__ int acc[kExplainTasks * kExplainBins];
+  for (int i = threadIdx.x; i < kExplainTasks * kExplainBins; i += kBlock) acc[i] = 0;
+  __syncthreads();
+  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+  int n = (blockIdx.y * kWavesPerBlock + wave) * kWave + lane;
+  const bool live = n < t.n;
+  if (!live) n = -1;
+  const int k0 = blockIdx.x * kExplainTasks, kend = min(k0 + kExplainTasks, n_tasks);
+  if (__ballot(live)) {  // (wave-uniform: a wave wholly past N skips the walk, not the barriers)
+    NodeRegs nr;
+    load_node(t, n, &nr);
+    for (int k = k0; k < kend; ++k) {
+      int code = 0;
+      unsigned reason = 0;
+      const bool ok = live && eval_pair(s, task_spec[k], task_pin[k], n, nr, pre_mask, filt_mask, &code, &reason);
+      const int bin = !live ? -1 : ok ? 9 : code == 255 ? 10 : code;
+      if (!live) reason = 0;
+      int mine = 0;
+#pragma unroll
+      for (int b = 0; b <= 10; ++b) {
+        const int c = __popcll(__ballot(bin == b));
+        if (lane == b) mine = c;
+      }
+      if (__ballot(reason != 0)) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const int c = __popcll(__ballot((reason >> b) & 1u));
+          if (lane == 12 + b) mine = c;
+        }
+#pragma unroll
+        for (int r = 0; r < kMaxR; ++r) {
+          const int c = __popcll(__ballot((reason >> (8 + r)) & 1u));
+          if (lane == 16 + r) mine = c;
+        }
+      }
+      if (lane < kExplainBins && mine) atomicAdd(&acc[(k - k0) * kExplainBins + lane], mine);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < (kend - k0) * kExplainBins; i += kBlock) {
+    const int v = acc[i];
+    if (v) atomicAdd(&bins[(size_t)k0 * kExplainBins + i], v);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // incremental column patch: only the bitmap columns of the listed (updated) nodes are re-evaluated
 // ---------------------------------------------------------------------------------------------------

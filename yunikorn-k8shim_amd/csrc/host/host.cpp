@@ -3209,6 +3209,138 @@ int32_t ykhost_is_pod_fit_node_via_preemption(ykhost_t* h, const char* allocatio
   return ykhost_preemption_predicates(h, it->second->row, nt->second, preempt_allocation_keys, num_keys, start_index);
 }
 
+// ---- why an ask fits nowhere (ykpred_explain) -----------------------------------------------------------------------------------
+// kube-scheduler's FitError text over the bins of ykpred_explain: "<fit>/<total> nodes are available: <count> <reason>, ...". The
+// wording is upstream's as upstream documents it (framework.FitError.Error: reasons counted over the nodes, the "<count> <reason>"
+// strings sorted AS STRINGS — "10 x" before "2 y" — and joined with ", "); upstream wording, not reference-held: the reference holds no
+// vector for it. The reason texts are compose_message's, so that a summary line agrees with the per-pair messages. Out of scope: the
+// per-taint "{key: value}" breakdown of the taint entry — upstream names the first untolerated taint in each node's OWN taint order,
+// which the dictionary encoding does not keep; every taint rejection is counted under the generic text.
+std::string explain_text(ykhost* h, const int32_t* b) {
+  int64_t total = 0;
+  for (int i = 0; i <= 10; ++i) total += b[i];
+  if (total == 0) return "no nodes available to schedule pods";
+  std::map<std::string, int64_t> reasons;  // same text => one entry
+  auto add = [&](const std::string& text, int64_t count) {
+    if (count > 0) reasons[text] += count;
+  };
+  add("node(s) didn't match Pod's node affinity/selector", b[0]);
+  add("node(s) were unschedulable", b[1]);
+  add("node(s) didn't match the requested node name", b[2]);
+  add("node(s) had untolerated taint", b[3]);
+  add("node not eligible", b[13]);
+  add("node(s) didn't match Pod's node affinity/selector", (int64_t)b[4] - b[13]);
+  add("node(s) didn't have free ports for the requested pod ports", b[5]);
+  add("Too many pods", b[12]);
+  static const char* base[] = {"cpu", "memory", "ephemeral-storage"};
+  bool fit_reasons = b[12] != 0;
+  for (int r = 0; r < 8; ++r) {
+    fit_reasons = fit_reasons || b[16 + r] != 0;
+    if (b[16 + r] <= 0) continue;
+    if (r >= 3 && (size_t)(r - 3) >= h->enc.scalar_names.size()) {
+      // the names are the encoder's: objects that arrived since the last encode have not named their resources yet
+      if (h->device < 0) {  // (a mirror-only handle encodes without a device, like ykhost_ask_supported)
+        EncodedTables T;
+        encode_tables(h, &T);
+        h->dirty_all = true;
+      } else {
+        sync(h);
+      }
+    }
+    add(std::string("Insufficient ") + (r < 3 ? std::string(base[r])
+                                         : (size_t)(r - 3) < h->enc.scalar_names.size() ? h->enc.scalar_names[(size_t)r - 3]
+                                                                                        : "resource #" + std::to_string(r)),
+        b[16 + r]);
+  }
+  // (NodeResourcesFit's Filter without its PreFilter in the list: the only code-6 verdict without a reason)
+  if (!fit_reasons) add("running \"NodeResourcesFit\" filter plugin: reading \"PreFilterNodeResourcesFit\" from cycleState: not found", b[6]);
+  add("node(s) didn't match pod topology spread constraints (missing required label)", b[15]);
+  add("node(s) didn't match pod topology spread constraints", (int64_t)b[7] - b[15]);
+  add("node(s) didn't match pod affinity/anti-affinity rules", b[8]);
+  add("node(s) not evaluated: the ask is routed to the CPU predicate manager", b[10]);
+  std::vector<std::string> entries;
+  for (auto& kv : reasons) entries.push_back(std::to_string(kv.second) + " " + kv.first);
+  std::sort(entries.begin(), entries.end());
+  std::string m = std::to_string(b[9]) + "/" + std::to_string(total) + " nodes are available";
+  for (size_t i = 0; i < entries.size(); ++i) m += (i ? ", " : ": ") + entries[i];
+  return m + ".";
+}
+
+int64_t ykhost_explain_format(ykhost_t* h, const int32_t* bins, char* out, int64_t len) {
+  YKHOST_LOCKED(h);
+  if (!bins) return fail(h, "explain_format: bad argument", -1);
+  const std::string m = explain_text(h, bins);
+  copy_out(m, out, len);
+  return (int64_t)m.size() + 1;
+}
+
+int32_t ykhost_explain(ykhost_t* h, int32_t n, const int32_t* asks, int32_t allocate, int32_t* out_bins) {
+  YKHOST_LOCKED(h);
+  if (n < 0 || (n > 0 && !out_bins)) return fail(h, "explain: bad argument", -1);
+  if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
+  int rc = sync(h);
+  if (rc) return rc;
+  const int P = (int)h->pending.size();
+  for (int i = 0; i < n; ++i)
+    if ((asks ? asks[i] : i) < 0 || (asks ? asks[i] : i) >= P) return fail(h, "explain: ask index out of range", YKPRED_E_INVALID);
+  const uint32_t pre = allocate ? h->alloc_pre : h->res_pre, filt = allocate ? h->alloc_filt : h->res_filt;
+  // An ask routed to the CPU manager is not evaluated: [10] = N without a device call. On a node-sharded handle the call is collective
+  // and the shards' dictionaries may route different asks, so every ask goes to the engine there — it answers the same row for a spec
+  // it does not evaluate, summed over the shards.
+  int32_t world = 1;
+  ykpred_comm_info(h->eng, nullptr, &world, nullptr);
+  std::vector<int32_t> list, slot;
+  list.reserve((size_t)n);
+  slot.reserve((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const int row = asks ? asks[i] : i;
+    int32_t* b = out_bins + (size_t)i * YKPRED_EXPLAIN_BINS;
+    if (world <= 1 && h->enc.unsupported.count(h->pending[(size_t)row]->tpl)) {
+      std::fill(b, b + YKPRED_EXPLAIN_BINS, 0);
+      b[10] = (int32_t)h->nodes.size();
+    } else {
+      list.push_back(row);
+      slot.push_back(i);
+    }
+  }
+  if (list.empty() && world <= 1) return 0;
+  std::vector<int32_t> rows(list.size() * (size_t)YKPRED_EXPLAIN_BINS);
+  rc = ykpred_explain(h->eng, (int32_t)list.size(), list.data(), pre, filt, rows.data());
+  if (rc) return fail(h, std::string("ykpred_explain: ") + ykpred_last_error(h->eng), rc);
+  for (size_t k = 0; k < list.size(); ++k)
+    memcpy(out_bins + (size_t)slot[k] * YKPRED_EXPLAIN_BINS, rows.data() + k * YKPRED_EXPLAIN_BINS, YKPRED_EXPLAIN_BINS * sizeof(int32_t));
+  return 0;
+}
+
+// The Message of the PodScheduled=False / Unschedulable condition for one ask, named as the core names it (allocation key = pod UID).
+int64_t ykhost_explain_message(ykhost_t* h, const char* allocation_key, int32_t allocate, char* out, int64_t len) {
+  YKHOST_LOCKED(h);
+  copy_out("", out, len);
+  ensure_uid_index(h);
+  auto it = h->by_uid.find(allocation_key ? allocation_key : "");
+  if (it == h->by_uid.end()) {
+    copy_out("predicates were not run because pod was not found in cache", out, len);  // ErrorPodNotFound (context.go:67)
+    return YKHOST_E_POD_NOT_FOUND;
+  }
+  if (!it->second->ask) {
+    copy_out("pod is cached but holds no row of the ask table (it is bound, not a pending ask)", out, len);
+    return fail(h, "pod holds no ask row", YKHOST_E_NOT_AN_ASK);
+  }
+  if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
+  int rc = sync(h);
+  if (rc) return rc;
+  auto un = h->enc.unsupported.find(it->second->tpl);
+  if (un != h->enc.unsupported.end()) {
+    copy_out(un->second, out, len);
+    return fail(h, "ask is not evaluated by the engine (route it to the CPU predicate manager): " + un->second, YKHOST_E_UNSUPPORTED);
+  }
+  int32_t bins[YKPRED_EXPLAIN_BINS];
+  const int32_t row = it->second->row;
+  rc = ykhost_explain(h, 1, &row, allocate, bins);
+  if (rc) return rc;
+  return ykhost_explain_format(h, bins, out, len);
+}
+
 int32_t ykhost_pod_request_json(ykhost_t* h, int32_t pod, char* out, int32_t len) {
   YKHOST_LOCKED(h);
   if (pod < 0 || pod >= (int)h->pending.size()) return fail(h, "index out of range");

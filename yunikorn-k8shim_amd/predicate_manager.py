@@ -31,6 +31,10 @@ ALL_PLUGINS = 0xFF
 OUT_BITMAP, OUT_COUNTS, OUT_DECISIONS, OUT_DECISION_KEYS = 1, 2, 4, 8
 EVAL_PROFILE, EVAL_DIRECT = 1 << 8, 1 << 9
 EVAL_SPREAD_COUNT_ONLY, EVAL_SPREAD_COUNTS_READY = 1 << 10, 1 << 11
+# ykpred_explain: int32[EXPLAIN_BINS] per ask — [0..8] first failing plugin code, [EXPLAIN_FIT] nodes the ask fits,
+# [EXPLAIN_UNSUPPORTED] nodes not evaluated (routed ask), [EXPLAIN_REASON0 + b] reason bit b, [EXPLAIN_RESOURCE0 + r] insufficient resource r
+EXPLAIN_BINS = 32
+EXPLAIN_FIT, EXPLAIN_UNSUPPORTED, EXPLAIN_REASON0, EXPLAIN_RESOURCE0 = 9, 10, 12, 16
 
 
 def plugin_mask(names):
@@ -582,6 +586,77 @@ class GpuPredicateManager:
         self._pcheck(self._P.ykpred_query(self.engine, len(pa), pa.ctypes.data, na.ctypes.data, pre, filt, fit.ctypes.data,
                                           code.ctypes.data, reason.ctypes.data))
         return fit, code, reason
+
+    def query_pod_packed(self, pod, allocate=True, pre_mask=None, filt_mask=None):
+        """Every Predicates() answer of ONE ask, one uint32 per node (ykpred_query_pod_packed): bits 0-7 plugin code, bit 8 fit,
+        bits 9-12 reason bits 0-3, bits 13.. the insufficient-resource bits. Explicit masks go to the engine directly, like query."""
+        p = pod if isinstance(pod, (int, np.integer)) else self.pod_index(pod)
+        self.sync()
+        pre, filt = self._explicit_masks(allocate, pre_mask, filt_mask)
+        out = np.zeros(max(self.layout().num_nodes, 1), dtype=np.uint32)
+        self._pcheck(self._P.ykpred_query_pod_packed(self.engine, int(p), pre, filt, out.ctypes.data))
+        return out[:self.layout().num_nodes]
+
+    def _explicit_masks(self, allocate, pre_mask, filt_mask):
+        pre = (self._masks[1] if allocate else self._masks[0]) if pre_mask is None else pre_mask
+        filt = (self._masks[3] if allocate else self._masks[2]) if filt_mask is None else filt_mask
+        return pre, filt
+
+    # ---- why an ask fits nowhere ---------------------------------------------------------------------------------
+    def explain(self, pods=None, allocate=True, pre_mask=None, filt_mask=None):
+        """Per ask the histogram of its Predicates() verdicts over ALL nodes, reduced on the device (ykpred_explain):
+        np.int32[n, EXPLAIN_BINS]. pods: ask indices or UIDs in any order, repeats allowed; None = every ask. Needs no evaluation
+        and disturbs none. An ask routed to the CPU manager gets [EXPLAIN_UNSUPPORTED] = N. Explicit masks go to ykpred_explain
+        directly, like query."""
+        if pods is None:
+            count, ptr = self.num_pods, None
+        else:
+            idx = [p if isinstance(p, (int, np.integer)) else self.pod_index(p) for p in pods]
+            arr = np.ascontiguousarray(idx, dtype=np.int32)
+            count, ptr = len(arr), arr.ctypes.data
+        out = np.zeros((max(count, 1), EXPLAIN_BINS), dtype=np.int32)
+        if pre_mask is None and filt_mask is None:
+            self._check(self._L.ykhost_explain(self._h, count, ptr, 1 if allocate else 0, out.ctypes.data))
+        else:
+            self.sync()
+            pre, filt = self._explicit_masks(allocate, pre_mask, filt_mask)
+            if ptr is None:
+                arr = np.arange(count, dtype=np.int32)
+                ptr = arr.ctypes.data
+            self._pcheck(self._P.ykpred_explain(self.engine, count, ptr, pre, filt, out.ctypes.data))
+        return out[:count].copy()
+
+    def explain_format(self, bins):
+        """kube-scheduler's FitError text for one row of explain(): "0/5 nodes are available: 2 Insufficient cpu, ..."
+        (ykhost_explain_format; a pure function of the bins and the resource names — works without a device)."""
+        b = np.ascontiguousarray(bins, dtype=np.int32)
+        if b.shape != (EXPLAIN_BINS,):
+            raise ValueError(f"explain_format takes one row of {EXPLAIN_BINS} bins")
+        need = self._check(self._L.ykhost_explain_format(self._h, b.ctypes.data, None, 0))
+        buf = C.create_string_buffer(need)
+        self._check(self._L.ykhost_explain_format(self._h, b.ctypes.data, buf, need))
+        return buf.value.decode()
+
+    def explain_message(self, pod, allocate=True):
+        """The Message of the PodScheduled=False / Unschedulable condition for one ask (index or UID): explain + format in one
+        crossing (ykhost_explain_message). Raises UnsupportedAsk for an ask routed to the CPU manager, KeyError for an unknown pod."""
+        if isinstance(pod, (int, np.integer)):  # (the host names asks by UID: an index takes the two calls)
+            ok, why = self.ask_supported(int(pod))
+            if not ok:
+                raise UnsupportedAsk(why)
+            return self.explain_format(self.explain([int(pod)], allocate)[0])
+        uid = pod
+        buf = C.create_string_buffer(4096)
+        rc = self._L.ykhost_explain_message(self._h, uid.encode(), 1 if allocate else 0, buf, 4096)
+        if rc == -13:
+            raise UnsupportedAsk(buf.value.decode())
+        if rc in (-10, -12):
+            raise KeyError(buf.value.decode())
+        self._check(rc)
+        if rc > 4096:
+            buf = C.create_string_buffer(rc)
+            self._check(self._L.ykhost_explain_message(self._h, uid.encode(), 1 if allocate else 0, buf, rc))
+        return buf.value.decode()
 
     def round_info(self):
         """ykpred_get_round_info: how the allocation rounds so far were decided (in batches / by the sequential kernel)."""
