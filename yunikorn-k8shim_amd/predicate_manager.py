@@ -568,6 +568,13 @@ class GpuPredicateManager:
         self._pcheck(self._P.ykpred_read_scores(self.engine, out.ctypes.data))
         return out
 
+    def read_order(self):
+        """The bin-pack order of the last evaluation that produced decisions (ykpred_read_order): out[i] = the node at position i —
+        ascending score, ties by NodeID. Raises when no such order is current."""
+        out = np.zeros(self.layout().num_nodes, dtype=np.int32)
+        self._pcheck(self._P.ykpred_read_order(self.engine, out.ctypes.data))
+        return out
+
     def checksum(self):
         v = C.c_uint64(0)
         self._pcheck(self._P.ykpred_bitmap_checksum(self.engine, C.byref(v)))
