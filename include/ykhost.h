@@ -53,6 +53,9 @@ int32_t ykhost_remove_node(ykhost_t* h, const char* node_name);  /* → number o
  * Running clears the assumed mark, Failed / Succeeded drops the pod (:344-347,374-383). */
 int32_t ykhost_update_pod(ykhost_t* h, const char* pod_json);
 int32_t ykhost_remove_pod(ykhost_t* h, const char* uid);         /* → 1 removed, 0 unknown uid (:390-417) */
+/* Host ports follow framework.NodeInfo.UsedPorts, a SET of (ip, protocol, port): a pod that leaves its node takes its triples with
+ * it even where another pod of the node holds the identical triple (no kubelet admits two such pods); the next AddPod puts them
+ * back. A snapshot that is dumped and loaded again starts from the union of the pods' ports. */
 /* The two update hooks for MANY objects at once — what the start-up replay of the informer caches amounts to
  * (Context.InitializeState, /root/reference/pkg/cache/context.go:1411-1484: every node, then every pod). `text` holds `len`
  * bytes of JSON documents one after the other (newline- or comma-separated; the body of a JSON array works): one cgo crossing,

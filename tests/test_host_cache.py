@@ -231,3 +231,30 @@ def test_callbacks_report_the_sentinel_errors(cache):
     assert cache.is_pod_fit_node_via_preemption(POD1, "unknown", [POD1], 0) == (-1, False)
     with pytest.raises(RuntimeError, match="mirror-only"):  # a known pair needs the engine
         cache.is_pod_fit_node(POD1, HOST1, True)
+
+
+def test_used_ports_are_a_set_of_triples(cache):
+    """framework.NodeInfo.UsedPorts (HostPortInfo.Add / Remove) keeps (ip, protocol, port) triples without counting their holders:
+    RemovePod of ONE of two pods that hold the identical triple frees the port, as the oracle's NodeInfo::remove_pod does and
+    PreemptionPredicates sees it on the node's clone. Two different triples that overlap (0.0.0.0 and 10.0.0.1) are two entries.
+    Read from the node's port_bits of the encoded tables: bit k = the node conflicts with the k-th wanted port."""
+    def holder(uid, ip):
+        p = pod(uid, node_name=HOST1, phase="Running")
+        p["spec"]["containers"] = [{"name": "c", "ports": [dict({"hostPort": 80, "containerPort": 80}, **({"hostIP": ip} if ip else {}))]}]
+        return p
+
+    ask = pod("ask")
+    ask["spec"]["containers"] = [{"name": "c", "ports": [{"hostPort": 80, "hostIP": "10.0.0.1", "containerPort": 80}]}]
+    cache.update_node(node(HOST1))
+    cache.update_pod(ask)
+    occupied = lambda: cache.encoded_tables()["port_bits"][0] & 1   # noqa: E731
+    for uid in ("a", "b"):
+        cache.update_pod(holder(uid, "10.0.0.1"))
+    assert cache.encoded_tables()["KP"] == 1 and occupied() == 1
+    assert cache.remove_pod("a") and cache.node_pod_count(HOST1) == 1
+    assert occupied() == 0, "the identical triple stays used after its first holder has gone"
+    cache.update_pod(holder("c", "10.0.0.1"))   # AddPod puts the triple back
+    assert occupied() == 1
+    cache.update_pod(holder("w", None))         # 0.0.0.0:80 is another triple
+    assert cache.remove_pod("c") and occupied() == 1
+    assert cache.remove_pod("w") and occupied() == 0 and cache.node_pod_count(HOST1) == 1

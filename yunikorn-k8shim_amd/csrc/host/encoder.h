@@ -708,6 +708,17 @@ class Encoder {
           }
     }
   }
+  // The same from NodeInfo.UsedPorts, the set that AddPod / RemovePod keep (see NodeInfo::used_ports)
+  void encode_used_ports(const std::set<HostPort>& used, uint64_t* bits) const {
+    std::fill(bits, bits + KP, 0);
+    if (used.empty()) return;
+    for (size_t k = 0; k < port_dict.size(); ++k)
+      for (const HostPort& u : used)
+        if (host_ports_conflict(port_dict[k], u)) {
+          bits[k >> 6] |= 1ull << (k & 63);
+          break;
+        }
+  }
   void encode_wanted_ports(const PodTemplate& t, uint64_t* bits) const {
     std::fill(bits, bits + KP, 0);
     for (const HostPort& hp : template_host_ports(t)) {

@@ -605,7 +605,7 @@ int encode_tables(ykhost* h, EncodedTables* T) {
       h->enc.encode_node_spread(*h->nodes[n], d1.data(), s1.data());
       for (int k = 0; k < KD; ++k) T->domain[(size_t)k * N + n] = d1[(size_t)k];
       for (int k = 0; k < KS; ++k) T->selcount[(size_t)k * N + n] = s1[(size_t)k];
-      h->enc.encode_ports(h->nodes[n]->pods, p1.data());
+      h->enc.encode_used_ports(h->nodes[n]->used_ports, p1.data());
       for (int k = 0; k < KP; ++k) T->ports[(size_t)k * N + n] = p1[(size_t)k];
       for (int r = 0; r < R; ++r) {
         T->alloc[(size_t)r * N + n] = a1[(size_t)r];
@@ -986,7 +986,7 @@ int node_row_sync(ykhost* h, int n) {
     return full_sync(h);
   }
   std::vector<uint64_t> pb((size_t)h->enc.KP + 1);
-  h->enc.encode_ports(h->nodes[(size_t)n]->pods, pb.data());
+  h->enc.encode_used_ports(h->nodes[(size_t)n]->used_ports, pb.data());
   ykpred_nodes_t nt{};
   nt.count = 1;
   nt.domain_id = dom.data();
@@ -3104,6 +3104,8 @@ int32_t ykhost_resident_stats(ykhost_t* h, int64_t* out5) {
 
 // Appends the victim columns of one PreemptionPredicates query: request vectors, "really removed" flags (nil victims and
 // victims that are not on the node are ignored, predicate_manager.go:181-192) and the node's host-port bits after each removal.
+// The ports follow NodeInfo.RemovePod: the victim's (ip, protocol, port) triples leave the SET of used ports, whether or not
+// another pod of the node holds the same triple.
 static void append_victims(ykhost* h, const NodeInfo& ni, const char* const* victim_uids, int32_t nv, std::vector<int64_t>* vreq,
                            std::vector<uint8_t>* present, std::vector<uint64_t>* ports_after) {
   const int R = h->enc.R, KP = h->enc.KP;
@@ -3112,6 +3114,8 @@ static void append_victims(ykhost* h, const NodeInfo& ni, const char* const* vic
   present->resize(base + (size_t)nv, 0);
   ports_after->resize((base + (size_t)nv) * (size_t)std::max(KP, 1), 0);
   std::vector<const Pod*> remaining(ni.pods.begin(), ni.pods.end());
+  std::set<HostPort> used = ni.used_ports;
+  bool ports_changed = true;
   for (int i = 0; i < nv; ++i) {
     const Pod* v = nullptr;
     if (victim_uids && victim_uids[i])
@@ -3129,8 +3133,13 @@ static void append_victims(ykhost* h, const NodeInfo& ni, const char* const* vic
         auto it = r.scalar.find(h->enc.scalar_names[s]);
         if (it != r.scalar.end()) row[3 + s] = it->second;
       }
+      for (const HostPort& hp : template_host_ports(*v->tpl)) ports_changed = used.erase(hp) > 0 || ports_changed;
     }
-    if (KP) h->enc.encode_ports(remaining, ports_after->data() + (base + (size_t)i) * (size_t)KP);  // NodeInfo.UsedPorts after this step
+    if (!KP) continue;
+    uint64_t* bits = ports_after->data() + (base + (size_t)i) * (size_t)KP;  // NodeInfo.UsedPorts after this step
+    if (ports_changed) h->enc.encode_used_ports(used, bits);
+    else std::copy(bits - KP, bits, bits);
+    ports_changed = false;
   }
 }
 

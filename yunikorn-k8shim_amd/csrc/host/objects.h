@@ -10,7 +10,9 @@
 #include <cstdint>
 #include <map>
 #include <memory>
+#include <set>
 #include <string>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -65,6 +67,7 @@ struct PodAffinityTerm {  // v1.PodAffinityTerm of a required (anti)affinity rul
 struct HostPort {  // v1.ContainerPort with hostPort > 0; "" hostIP = 0.0.0.0, "" protocol = TCP (HostPortInfo.sanitize)
   std::string protocol, ip;
   int64_t port = 0;
+  bool operator<(const HostPort& o) const { return std::tie(ip, protocol, port) < std::tie(o.ip, o.protocol, o.port); }
 };
 struct Container {
   std::string name;
@@ -225,6 +228,9 @@ struct NodeInfo {
   std::vector<const Pod*> pods;
   Resource requested, allocatable;
   int32_t index = -1;  // engine node index
+  // NodeInfo.UsedPorts: a SET of (ip, protocol, port). AddPod inserts a pod's triples, RemovePod erases them — also a triple
+  // that another pod of the node still holds (upstream's HostPortInfo.Remove does not count holders)
+  std::set<HostPort> used_ports;
 
   void set_node(const Node& n) {
     node = n;
@@ -236,6 +242,15 @@ struct NodeInfo {
     requested.memory += sign * r.memory;
     requested.ephemeral += sign * r.ephemeral;
     for (auto& kv : r.scalar) requested.scalar[kv.first] += sign * kv.second;
+    for (auto& c : p->tpl->init_containers)
+      if (c.sidecar) account_ports(c.host_ports, sign);
+    for (auto& c : p->tpl->containers) account_ports(c.host_ports, sign);
+  }
+  void account_ports(const std::vector<HostPort>& ports, int sign) {
+    for (const HostPort& hp : ports) {
+      if (sign > 0) used_ports.insert(hp);
+      else used_ports.erase(hp);
+    }
   }
   void add_pod(const Pod* p) {
     pods.push_back(p);
