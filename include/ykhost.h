@@ -244,6 +244,21 @@ int32_t ykhost_explain(ykhost_t* h, int32_t n, const int32_t* asks /* NULL = ask
 int64_t ykhost_explain_format(ykhost_t* h, const int32_t* bins /* [32] */, char* out, int64_t len);
 int64_t ykhost_explain_message(ykhost_t* h, const char* allocation_key, int32_t allocate, char* out, int64_t len);
 
+/* HOW MANY copies of an ask the cluster can still place (ykpred.h: ykpred_headroom) — what the gang path otherwise learns by waiting
+ * out placeholderTimeoutInSeconds. Always with the ALLOCATION-phase plugin lists: the reservation lists carry no NodeResourcesFit.
+ *   ykhost_headroom         syncs and makes ONE engine call for the listed asks (NULL = asks 0..n-1): out_cells[i] = the
+ *                           YKPRED_HEADROOM_CELLS cells of ask i over all nodes. An ask routed to the CPU manager gets status [3] = 1
+ *                           without a device call. A mirror-only handle fails like every other evaluation. On a node-sharded handle
+ *                           the call is collective and the cells are cluster-wide.
+ *   ykhost_headroom_nodes   replicas of ONE ask on every node (ykpred_headroom_pod): which nodes take how many copies; -1 everywhere
+ *                           for a coupled ask, 0 everywhere for a routed one; this shard's nodes on a node-sharded handle.
+ *   ykhost_headroom_by_key  ykhost_headroom for one ask by allocation key (pod UID). → 0, or YKHOST_E_POD_NOT_FOUND /
+ *                           YKHOST_E_NOT_AN_ASK as ykhost_is_pod_fit_node, YKHOST_E_UNSUPPORTED (with out16[3] = 1) for an ask the
+ *                           engine does not evaluate. */
+int32_t ykhost_headroom(ykhost_t* h, int32_t n, const int32_t* asks /* NULL = asks 0..n-1 */, int64_t* out_cells /* [n][16] */);
+int32_t ykhost_headroom_nodes(ykhost_t* h, int32_t pod, int32_t* out /* [N] */);
+int32_t ykhost_headroom_by_key(ykhost_t* h, const char* allocation_key, int64_t* out16 /* [16] */);
+
 /* Engine calls that came back YKPRED_E_DEVICE / YKPRED_E_NOMEM so far (failed allocation, lost device). Each one marks the whole
  * device state stale: the failing call returns its error (Predicates() < 0: the Go manager routes the ask to the CPU predicate
  * manager — SURVEY.md §5, "must degrade, never fail scheduling"), the mirror stays intact, and the next ykhost_sync /

@@ -38,7 +38,9 @@
 extern "C" {
 #endif
 
-/* (ykpred_explain + YKPRED_EXPLAIN_BINS arrived WITHIN version 4, without a bump: a host that needs the call detects it by the
+/* (ykpred_headroom + ykpred_headroom_pod + YKPRED_HEADROOM_CELLS arrived WITHIN version 4 as well, detected the same way:
+ *    dlsym("ykpred_headroom"))
+ * (ykpred_explain + YKPRED_EXPLAIN_BINS arrived WITHIN version 4, without a bump: a host that needs the call detects it by the
  *    exported symbol — dlsym("ykpred_explain") — not by the version number)
  * 4: ykpred_set_spec_effects + ykpred_spec_effects_t, ykpred_comm_info (round 5 added them without a bump: a host built against the
  *    header could not tell an older library apart), ykpred_layout_t.sweep_rows / index_rows_walked / run_rows / fused_rows, ykpred_get_round_info
@@ -463,6 +465,46 @@ int32_t ykpred_query_pod_packed(ykpred_engine_t* e, int32_t pod_index, uint32_t 
  *   blocking in the reduce. */
 int32_t ykpred_explain(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks /* host, ask indices, any order, repeats allowed */,
                        uint32_t prefilter_plugins, uint32_t filter_plugins, int32_t* out /* host, [n_asks][YKPRED_EXPLAIN_BINS] */);
+
+/* HOW MANY copies of an ask the cluster can still place — the question of the gang path: the shim creates minMember identical
+ * placeholders per task group and then waits out placeholderTimeoutInSeconds to learn whether the gang could be placed.
+ * replicas(a, n) = the largest k such that k copies of ask a, assumed one after another on node n while no other node changes, each
+ * pass Predicates() under the given plugin lists at the moment it is placed:
+ *   0 when the pair does not fit (exactly ykpred_query's verdict: the kernels call the same per-pair routine); otherwise
+ *   k0 = min(allowed_pods[n] - pod_count[n], min over r with request_r > 0 of floor((allocatable_r[n] - requested_r[n]) / request_r))
+ *   in exact int64 arithmetic, and k = min(k0, 1) when the spec requests a dictionary host port and NodePorts is in both lists (a pod
+ *   conflicts with its own (ip, protocol, port)), else k = k0. k >= 1 whenever the pair fits, and k fits an int32 (the pod slots bound it).
+ * The BINDER of a node with k >= 1: the host port when it cut k0 > 1 down to 1; else the lowest r whose quotient equals k0; else the
+ * pod slots. */
+#define YKPRED_HEADROOM_CELLS 16
+/* per ask, int64[16], over all nodes of the table:
+ *  [0]      sum of replicas over the nodes
+ *  [1]      nodes with replicas >= 1 (== bin [9] of ykpred_explain)
+ *  [2]      max of replicas over the nodes
+ *  [3]      status: 0 computed; 1 the ask's spec is YKPRED_SPEC_UNSUPPORTED (every other cell 0); 2 COUPLED
+ *  [4]      nodes bound by their pod slots
+ *  [5]      nodes bound by the host port
+ *  [6], [7] 0
+ *  [8 + r]  nodes bound by resource r, r = 0..7
+ * COUPLED: the spec has a topology signature and a topology plugin is enabled (PodTopologySpread in the Filter list, or
+ *   InterPodAffinity in both lists) — the verdicts read the topology histograms, so copies change each other's verdicts across nodes
+ *   and no per-node quotient describes them: [0] = [2] = -1, [1] is still the single-copy fit count, the binder cells are 0.
+ * Invariants at status 0: [4] + [5] + [8] + ... + [15] == [1]; [1] <= [0]; [2] <= [0].
+ * The figure is an upper bound while other asks compete for the same nodes.
+ * Everything else is ykpred_explain's: the listed asks are reduced to their distinct (spec, NodeName) tasks; the call reads the TABLES
+ *   only, needs no evaluation and invalidates none; it prepares the topology histograms as ykpred_query does; it counts as one query;
+ *   roctx range "ykpred:headroom"; YKPRED_E_INVALID for a bad pointer or an index out of range, YKPRED_E_STATE before the tables are
+ *   uploaded, n_asks == 0 returns YKPRED_OK, a table of N == 0 nodes gives all-zero rows. Additionally YKPRED_E_INVALID unless
+ *   NodeResourcesFit is in BOTH lists: without it nothing bounds k.
+ * NODE-SHARDED engines: COLLECTIVE like ykpred_explain (the same agreement all-gather first), then one all-reduce SUM (int64) of the
+ *   [tasks][16] table and one all-reduce MAX (int64) of the [tasks] maxima, which the device keeps in an array of their own: every rank
+ *   returns CLUSTER-WIDE cells. */
+int32_t ykpred_headroom(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks /* host, ask indices, any order, repeats allowed */,
+                        uint32_t prefilter_plugins, uint32_t filter_plugins, int64_t* out /* host, [n_asks][YKPRED_HEADROOM_CELLS] */);
+/* replicas(pod, n) for every node n of the table (thread = node, as ykpred_query_pod): which nodes take how many copies. -1 in every
+ * cell for a coupled ask, 0 everywhere for a YKPRED_SPEC_UNSUPPORTED spec. On a node-sharded engine: this shard's nodes only, nothing
+ * is exchanged. Errors as ykpred_query_pod, plus YKPRED_E_INVALID unless NodeResourcesFit is in both lists. */
+int32_t ykpred_headroom_pod(ykpred_engine_t* e, int32_t pod_index, uint32_t prefilter_plugins, uint32_t filter_plugins, int32_t* out /* [N] */);
 
 /* PreemptionPredicates (predicate_manager.go:141-179): victims are described by their request vectors, in order. */
 int32_t ykpred_preemption(ykpred_engine_t* e, int32_t pod_index, int32_t node_index, int32_t num_victims,

@@ -446,6 +446,41 @@ func (m *gpuPredicateManager) ExplainUnschedulable(pod *v1.Pod, allocate bool) (
 	}
 }
 
+// Headroom answers "how many copies of this ask can the cluster still place" — the figure the gang path otherwise learns by waiting
+// out placeholderTimeoutInSeconds: total = the sum over all nodes of the copies each node takes (free columns divided by the request
+// vector, bounded by the free pod slots; ykpred_headroom reduces it on the device), nodes = how many nodes take at least one, most =
+// the most a single node takes. ONE crossing: ykhost_headroom_by_key looks the ask up by allocation key and runs the reduction with
+// the allocation-phase plugin lists. Asked for ONE placeholder of a task group it is an upper bound for the group's minMember while
+// other groups compete for the same nodes (INTEGRATION.md names the call site). ok == false when the pod is not a mirrored ask, is
+// routed to the CPU predicate manager, the engine failed, or the ask is COUPLED (a hard spread constraint or inter-pod (anti)affinity
+// makes its copies interact across nodes: no per-node figure describes them) — the caller then waits as it does today.
+func (m *gpuPredicateManager) Headroom(pod *v1.Pod) (total, nodes, most int64, ok bool) {
+	if pod == nil {
+		return 0, 0, 0, false
+	}
+	var cells [16]C.int64_t
+	uid := C.CString(string(pod.UID))
+	rc := C.ykhost_headroom_by_key(m.host, uid, &cells[0])
+	C.free(unsafe.Pointer(uid))
+	switch {
+	case rc == 0 && cells[3] == 0:
+		return int64(cells[0]), int64(cells[1]), int64(cells[2]), true
+	case rc == 0:
+		return 0, int64(cells[1]), 0, false
+	case rc == C.YKHOST_E_UNSUPPORTED:
+		m.Counters.RoutedUnsupported.Add(1)
+		return 0, 0, 0, false
+	case rc == C.YKHOST_E_POD_NOT_FOUND || rc == C.YKHOST_E_NOT_AN_ASK:
+		m.Counters.RoutedNotMirrored.Add(1)
+		return 0, 0, 0, false
+	default:
+		m.Counters.RoutedOnError.Add(1)
+		log.Log(log.ShimPredicates).Warn("GPU predicate engine error, no headroom figure for the ask",
+			zap.String("error", C.GoString(C.ykhost_last_error(m.host))))
+		return 0, 0, 0, false
+	}
+}
+
 // ResidentStats: Predicates() calls answered from the mirrored resident answer, per pair because the node's column changed,
 // by whole-ask device queries, and the answer / failing-plugin fetches behind them.
 func (m *gpuPredicateManager) ResidentStats() (resident, dirtyColumn, query, answerFetches, codeFetches int64) {

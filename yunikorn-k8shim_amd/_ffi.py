@@ -135,6 +135,8 @@ def load_ykpred():
     L.ykpred_read_class_rows.argtypes = [C.c_void_p, C.c_void_p]
     L.ykpred_query_pod_packed.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
     L.ykpred_explain.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.ykpred_headroom.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.ykpred_headroom_pod.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
     _pred = L
     return L
 
@@ -208,6 +210,9 @@ def load_ykhost():
     L.ykhost_explain_format.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64]
     L.ykhost_explain_message.restype = C.c_int64
     L.ykhost_explain_message.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_char_p, C.c_int64]
+    L.ykhost_headroom.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.ykhost_headroom_nodes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    L.ykhost_headroom_by_key.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     L.ykhost_device_errors.restype = C.c_int64
     L.ykhost_device_errors.argtypes = [C.c_void_p]
     _host = L

@@ -274,6 +274,7 @@ struct ykpred_engine {
   int index_rows_needed = 0;         // index rows some class OUTSIDE the sweep runs reads (the full pass walks only those)
   DevBuf d_agree;  // sharded rounds: what the ranks agree on before the first batch
   DevBuf d_explain;  // ykpred_explain: task specs | task pins | [tasks][YKPRED_EXPLAIN_BINS] counts
+  DevBuf d_headroom;  // ykpred_headroom: [tasks][YKPRED_HEADROOM_CELLS] cells | [tasks] max replicas | task specs | task pins
   DevBuf d_bytes_gather;  // ykpred_comm_allgather_bytes
   DevBuf d_topo_agree;  // node-sharded: the shape of every rank's topology histograms (agree_topology)
   u64 dict_digest = 0;  // ykpred_set_dictionary_digest
@@ -4528,6 +4529,165 @@ int32_t ykpred_explain(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, 
   HIPCHK(hipMemcpyAsync(rows.data(), d_bins, T * B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   for (int i = 0; i < n_asks; ++i) memcpy(out + (size_t)i * B, rows.data() + (size_t)task_of[(size_t)i] * B, B * sizeof(int32_t));
+  return YKPRED_OK;
+}
+
+// Copies of an ask are COUPLED when its verdicts read the topology histograms — the condition under which eval_pair enters
+// constraints_fail: a placed copy then changes the verdicts of the next one on other nodes too, and a per-node quotient says nothing.
+static bool headroom_coupled(const ykpred_engine* e, int32_t spec, uint32_t pre, uint32_t filt) {
+  const bool spread_en = filt & YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD;
+  const bool ipa_en = (filt & YKPRED_PLUGIN_INTER_POD_AFFINITY) && (pre & YKPRED_PLUGIN_INTER_POD_AFFINITY);
+  return (spread_en || ipa_en) && (size_t)spec < e->spec_sig_spread.size() && e->spec_sig_spread[(size_t)spec] >= 0;
+}
+
+// How many copies of an ask the cluster still takes: per listed ask the per-node replicas (kernels.hip.h: replicas) reduced over every
+// node on the device (k_headroom). The shape of ykpred_explain — tasks, agreement, one reduce — with an int64 table and a max beside it.
+int32_t ykpred_headroom(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, uint32_t pre, uint32_t filt, int64_t* out) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:headroom");
+  if (e) e->n_queries++;
+  static_assert(ykk::kHeadroomCells == YKPRED_HEADROOM_CELLS, "k_headroom writes the layout of ykpred.h");
+  constexpr size_t B = YKPRED_HEADROOM_CELLS;
+  if (!e) return YKPRED_E_INVALID;
+  const bool sharded = e->comm && e->comm_world > 1;
+  int rc = YKPRED_OK;
+  const char* why = "";
+  if (n_asks < 0 || (n_asks > 0 && (!asks || !out))) rc = YKPRED_E_INVALID, why = "headroom: bad argument";
+  else if (!(pre & filt & YKPRED_PLUGIN_NODE_RESOURCES_FIT)) rc = YKPRED_E_INVALID, why = "headroom: NodeResourcesFit must be in both plugin lists (nothing else bounds the count)";
+  else if (!e->nodes_set || !e->specs_set || !e->pods_set) rc = YKPRED_E_STATE, why = "headroom: tables not uploaded";
+  else
+    for (int i = 0; i < n_asks; ++i)
+      if (asks[i] < 0 || asks[i] >= e->P) rc = YKPRED_E_INVALID, why = "headroom: index out of range";
+  if (!sharded && rc != YKPRED_OK) return fail(e, rc, why);
+  if (!sharded && n_asks == 0) return YKPRED_OK;
+  // Tasks: the distinct (spec, pin) of the list, keyed as ykpred_explain keys them (a sharded engine cannot key on the pin, a node index
+  // of ITS shard; with by_ask every distinct ask index is a task — the keys every rank derives alike).
+  std::vector<int32_t> task_of, t_spec, t_pin;
+  auto build_tasks = [&](bool by_ask) {
+    std::unordered_map<u64, int32_t> index;
+    task_of.assign((size_t)n_asks, 0);
+    t_spec.clear();
+    t_pin.clear();
+    for (int i = 0; i < n_asks; ++i) {
+      const int32_t a = asks[i], sp = e->h_pod_spec[(size_t)a], pin = e->h_pod_pin[(size_t)a];
+      u64 key = ((u64)(uint32_t)sp << 32) | (u64)(uint32_t)pin;
+      if (by_ask || (sharded && pin != YKPRED_NO_NODE_NAME)) key = (1ull << 63) | (u64)(uint32_t)a;
+      auto it = index.emplace(key, (int32_t)t_spec.size());
+      if (it.second) {
+        t_spec.push_back(sp);
+        t_pin.push_back(pin);
+      }
+      task_of[(size_t)i] = it.first->second;
+    }
+  };
+  if (rc == YKPRED_OK) build_tasks(false);
+  HIPCHK(hipSetDevice(e->cfg.device));
+  hipStream_t st = e->own_stream;
+  if (rc == YKPRED_OK && e->N > 0 && n_asks > 0) {
+    // (the histogram preparation of ykpred_query: a coupled ask's fit count [1] reads them)
+    if ((pre & filt & (YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD | YKPRED_PLUGIN_INTER_POD_AFFINITY))) rc = ensure_histograms(e, st);
+    else if (e->spread_dirty) rc = build_spread_tables(e, st);
+    if (rc != YKPRED_OK && !sharded) return rc;
+  }
+  if (sharded) {
+    // Collective: (status, ask count, list, task partition) agreed before anybody enters the reduces, as in ykpred_explain.
+    struct Agree {
+      int32_t rc, n;
+      u64 list, partition;
+    };
+    Agree mine{rc, n_asks, 0x9e3779b97f4a7c15ull, 0x9e3779b97f4a7c15ull};
+    if (rc == YKPRED_OK)
+      for (int i = 0; i < n_asks; ++i) {
+        mine.list = (mine.list ^ (u64)(uint32_t)asks[i]) * 0x100000001b3ull;
+        mine.partition = (mine.partition ^ (u64)(uint32_t)task_of[(size_t)i]) * 0x100000001b3ull;
+      }
+    const int W = e->comm_world;
+    HIPCHK(e->d_agree.ensure((size_t)(W + 1) * sizeof(Agree)));
+    Agree* d = e->d_agree.as<Agree>();
+    HIPCHK(hipMemcpyAsync(d + W, &mine, sizeof(Agree), hipMemcpyHostToDevice, st));
+    NCCLCHK(rccl()->AllGather(d + W, d, sizeof(Agree), ncclInt8, e->comm, st));
+    std::vector<Agree> all((size_t)W);
+    HIPCHK(hipMemcpyAsync(all.data(), d, (size_t)W * sizeof(Agree), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int g = 0; g < W; ++g)
+      if (all[(size_t)g].rc != YKPRED_OK)
+        return fail(e, all[(size_t)g].rc, "headroom (sharded): rank " + std::to_string(g) + " cannot run the call (" +
+                                              (g == e->comm_rank && *why ? why : "bad argument, NodeResourcesFit missing from a list, tables not uploaded, an index out of range or stale topology histograms") +
+                                              "): no rank runs it");
+    for (int g = 0; g < W; ++g)
+      if (all[(size_t)g].n != all[0].n || all[(size_t)g].list != all[0].list)
+        return fail(e, YKPRED_E_INVALID, "headroom (sharded): rank " + std::to_string(g) + " was handed a different ask list: every rank passes the same asks");
+    if (n_asks == 0) return YKPRED_OK;
+    bool same = true;
+    for (int g = 0; g < W; ++g) same = same && all[(size_t)g].partition == all[0].partition;
+    if (!same) build_tasks(true);
+  }
+  const size_t T = t_spec.size();
+  HIPCHK(e->d_headroom.ensure(T * ((B + 1) * sizeof(int64_t) + 2 * sizeof(int32_t)) + 64));
+  int64_t* d_cells = e->d_headroom.as<int64_t>();  // (the table and the max first: what the reduces and the copy move)
+  int64_t* d_max = d_cells + T * B;
+  int32_t* d_spec = (int32_t*)(d_max + T);
+  int32_t* d_pin = d_spec + T;
+  HIPCHK(hipMemsetAsync(d_cells, 0, T * (B + 1) * sizeof(int64_t), st));
+  if (e->N > 0) {
+    HIPCHK(hipMemcpyAsync(d_spec, t_spec.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_pin, t_pin.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    const dim3 grid((unsigned)((T + ykk::kExplainTasks - 1) / ykk::kExplainTasks), (unsigned)((e->N + ykk::kBlock - 1) / ykk::kBlock));
+    hipLaunchKernelGGL(ykk::k_headroom, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e), (int)T, d_spec, d_pin, pre, filt,
+                       (ykk::i64*)d_cells, (ykk::i64*)d_max);
+    HIPCHK(hipGetLastError());
+  }
+  if (sharded) {
+    NCCLCHK(rccl()->AllReduce(d_cells, d_cells, T * B, ncclInt64, ncclSum, e->comm, st));
+    NCCLCHK(rccl()->AllReduce(d_max, d_max, T, ncclInt64, ncclMax, e->comm, st));
+  }
+  std::vector<int64_t> rows(T * (B + 1));
+  HIPCHK(hipMemcpyAsync(rows.data(), d_cells, T * (B + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  // The status per task, decided here: [3] arrives as the number of shards whose spec table does not evaluate the spec.
+  for (size_t k = 0; k < T; ++k) {
+    int64_t* row = rows.data() + k * B;
+    row[2] = rows[T * B + k];
+    if (row[3] != 0) {
+      std::fill(row, row + B, (int64_t)0);
+      row[3] = 1;
+    } else if (headroom_coupled(e, t_spec[k], pre, filt)) {
+      const int64_t fit = row[1];
+      std::fill(row, row + B, (int64_t)0);
+      row[0] = row[2] = -1;
+      row[1] = fit;
+      row[3] = 2;
+    }
+  }
+  for (int i = 0; i < n_asks; ++i) memcpy(out + (size_t)i * B, rows.data() + (size_t)task_of[(size_t)i] * B, B * sizeof(int64_t));
+  return YKPRED_OK;
+}
+
+// replicas of one ask on every node of this table (this shard's nodes on a sharded engine; nothing is exchanged)
+int32_t ykpred_headroom_pod(ykpred_engine_t* e, int32_t pod, uint32_t pre, uint32_t filt, int32_t* out) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:headroom_pod");
+  if (e) e->n_queries++;
+  if (!e || !out) return fail(e, YKPRED_E_INVALID, "headroom_pod: bad argument");
+  if (!(pre & filt & YKPRED_PLUGIN_NODE_RESOURCES_FIT)) return fail(e, YKPRED_E_INVALID, "headroom_pod: NodeResourcesFit must be in both plugin lists (nothing else bounds the count)");
+  if (!e->nodes_set || !e->specs_set || !e->pods_set) return fail(e, YKPRED_E_STATE, "headroom_pod: tables not uploaded");
+  if (pod < 0 || pod >= e->P) return fail(e, YKPRED_E_INVALID, "headroom_pod: index out of range");
+  if (e->N == 0) return YKPRED_OK;
+  const size_t N = (size_t)e->N;
+  const int32_t spec = e->h_pod_spec[(size_t)pod];
+  if (headroom_coupled(e, spec, pre, filt)) {  // no per-node figure exists for copies that interact across nodes
+    std::fill(out, out + N, (int32_t)-1);
+    return YKPRED_OK;
+  }
+  HIPCHK(hipSetDevice(e->cfg.device));
+  hipStream_t st = e->own_stream;
+  if (e->spread_dirty) TRY(build_spread_tables(e, st));
+  HIPCHK(e->d_scratch.ensure(N * sizeof(int32_t) + 64));
+  hipLaunchKernelGGL(ykk::k_headroom_pod, dim3((unsigned)((N + ykk::kBlock - 1) / ykk::kBlock)), dim3(ykk::kBlock), 0, st, node_table(e),
+                     spec_table(e), spec, e->h_pod_pin[(size_t)pod], pre, filt, e->d_scratch.as<int32_t>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, e->d_scratch.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
   return YKPRED_OK;
 }
 

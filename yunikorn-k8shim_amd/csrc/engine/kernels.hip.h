@@ -2944,6 +2944,119 @@ __global__ __launch_bounds__(kBlock) void k_explain(NodeTable t, SpecTable s, in
   }
 }
 
+// ykpred_headroom: how many copies of an ask a node still takes. replicas(a, n) = the largest k such that k copies of the ask, assumed one
+// after another on node n while no other node changes, each pass Predicates(): 0 when eval_pair rejects the pair, else
+// k0 = min(free pod slots, min over r with req_r > 0 of floor(free_r / req_r)) in exact int64 arithmetic (values reach 2^63 - 1: no
+// floating point), cut to 1 when the spec requests a dictionary host port and NodePorts is in both lists (a pod conflicts with its own
+// (ip, protocol, port)). A pair that fits has free_r >= req_r and a free slot, so k >= 1; the slots bound k, so it fits an int.
+// *binder says what bounds the node: kBindPort when the port cut k0 > 1 down to 1, else kBindRes0 + the lowest r whose quotient is k0,
+// else kBindSlots. `slots` = allowed - count, read beside load_node (NodeRegs keeps only slots_ok). NOT meaningful for a spec whose
+// verdicts read the topology histograms (copies then change each other's verdicts): the host marks those asks as coupled.
+constexpr int kHeadroomCells = 16;
+constexpr int kBindSlots = 4, kBindPort = 5, kBindRes0 = 8;  // (the cells of include/ykpred.h that count the nodes so bound)
+__device__ __forceinline__ int replicas(const SpecTable& s, int spec, int pin, int node, const NodeRegs& nr, i64 slots, unsigned pre_mask,
+                                        unsigned filt_mask, int* binder) {
+  int code = 0;
+  unsigned reason = 0;
+  *binder = 0;
+  if (!eval_pair(s, spec, pin, node, nr, pre_mask, filt_mask, &code, &reason)) return 0;
+  const i64* q = s.req + (size_t)spec * s.R;
+  i64 qmin = 0x7fffffffffffffffll;
+  int rmin = 0;
+#pragma unroll
+  for (int r = 0; r < kMaxR; ++r)
+    if (r < s.R && q[r] > 0) {  // (wave-uniform: the request vector is the task's)
+      const i64 quo = nr.fr[r] / q[r];
+      if (quo < qmin) qmin = quo, rmin = r;
+    }
+  i64 k = min(slots, qmin);
+  *binder = qmin <= slots ? kBindRes0 + rmin : kBindSlots;
+  if ((filt_mask & kPlugPorts) && (pre_mask & kPlugPorts)) {
+    bool any = false;
+#pragma unroll
+    for (int p = 0; p < kMaxKP; ++p)
+      if (p < s.KP) any = any || s.wanted_ports[(size_t)spec * s.KP + p] != 0;
+    if (any && k > 1) k = 1, *binder = kBindPort;
+  }
+  return (int)max((i64)1, k);  // (k >= 1 by the fit: NodeResourcesFit is in both lists, the host checked)
+}
+
+// Grid and walk of k_explain: blockIdx.x = chunk of kExplainTasks tasks, blockIdx.y = group of 4 node words, lane = node, the wave walks
+// the chunk's tasks. Per task and wave: Σ replicas by a wave reduction (at most 64 x 2^31 = 2^37), the node counts by ballot popcounts
+// (lane c keeps cell c), max replicas by a wave max. The block's waves meet in LDS; the block then issues one global integer add per
+// non-zero cell of cells[tasks][16] and one integer max per non-zero entry of maxk[tasks], both zeroed on the stream by the host. No
+// float anywhere: the result does not depend on the order of arrival. Cell [3] is written by the first node group alone: 1 for a spec
+// the engine does not evaluate (every other cell of such a task stays 0: eval_pair rejects every pair).
+__global__ __launch_bounds__(kBlock) void k_headroom(NodeTable t, SpecTable s, int n_tasks, const int* __restrict__ task_spec,
+                                                     const int* __restrict__ task_pin, unsigned pre_mask, unsigned filt_mask,
+                                                     i64* __restrict__ cells, i64* __restrict__ maxk) {
+  __shared__ i64 acc[kExplainTasks * kHeadroomCells];
+  __shared__ int accmax[kExplainTasks];
+  for (int i = threadIdx.x; i < kExplainTasks * kHeadroomCells; i += kBlock) acc[i] = 0;
+  if (threadIdx.x < kExplainTasks) accmax[threadIdx.x] = 0;
+  __syncthreads();
+  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+  int n = (blockIdx.y * kWavesPerBlock + wave) * kWave + lane;
+  const bool live = n < t.n;
+  if (!live) n = -1;
+  const int k0 = blockIdx.x * kExplainTasks, kend = min(k0 + kExplainTasks, n_tasks);
+  if (__ballot(live)) {  // (wave-uniform: a wave wholly past N skips the walk, not the barriers)
+    NodeRegs nr;
+    load_node(t, n, &nr);
+    const i64 slots = live ? (i64)t.allowed[n] - (i64)t.count[n] : 0;
+    for (int k = k0; k < kend; ++k) {
+      int binder = 0;
+      const int rep = live ? replicas(s, task_spec[k], task_pin[k], n, nr, slots, pre_mask, filt_mask, &binder) : 0;
+      const u64 fits = __ballot(rep > 0);
+      if (!fits) continue;  // (wave-uniform)
+      i64 sum = rep;
+      int mx = rep;
+#pragma unroll
+      for (int off = kWave / 2; off > 0; off >>= 1) {
+        sum += (i64)__shfl_xor((long long)sum, off, kWave);
+        mx = max(mx, __shfl_xor(mx, off, kWave));
+      }
+      i64 mine = lane == 0 ? sum : lane == 1 ? (i64)__popcll(fits) : 0;
+      {
+        const int c = __popcll(__ballot(rep > 0 && binder == kBindSlots));
+        if (lane == kBindSlots) mine = c;
+      }
+      {
+        const int c = __popcll(__ballot(rep > 0 && binder == kBindPort));
+        if (lane == kBindPort) mine = c;
+      }
+#pragma unroll
+      for (int r = 0; r < kMaxR; ++r) {
+        const int c = __popcll(__ballot(rep > 0 && binder == kBindRes0 + r));
+        if (lane == kBindRes0 + r) mine = c;
+      }
+      if (lane < kHeadroomCells && mine) atomicAdd((u64*)&acc[(k - k0) * kHeadroomCells + lane], (u64)mine);
+      if (lane == 0) atomicMax(&accmax[k - k0], mx);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < (kend - k0) * kHeadroomCells; i += kBlock) {
+    const i64 v = acc[i];
+    if (v) atomicAdd((u64*)&cells[(size_t)k0 * kHeadroomCells + i], (u64)v);
+  }
+  if ((int)threadIdx.x < kend - k0) {
+    const int v = accmax[threadIdx.x];
+    if (v) atomicMax((long long*)&maxk[k0 + threadIdx.x], (long long)v);
+    if (blockIdx.y == 0 && (s.flags[task_spec[k0 + threadIdx.x]] & kSpecUnsupported)) cells[(size_t)(k0 + threadIdx.x) * kHeadroomCells + 3] = 1;
+  }
+}
+
+// replicas of ONE ask on every node of the table (thread = node, as k_query_pod): which nodes take how many copies
+__global__ __launch_bounds__(kBlock) void k_headroom_pod(NodeTable t, SpecTable s, int spec, int pin, unsigned pre_mask, unsigned filt_mask,
+                                                         int* __restrict__ out) {
+  int n = blockIdx.x * kBlock + threadIdx.x;
+  if (n >= t.n) return;
+  NodeRegs nr;
+  load_node(t, n, &nr);
+  int binder = 0;
+  out[n] = replicas(s, spec, pin, n, nr, (i64)t.allowed[n] - (i64)t.count[n], pre_mask, filt_mask, &binder);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // incremental column patch: only the bitmap columns of the listed (updated) nodes are re-evaluated
 // ---------------------------------------------------------------------------------------------------

@@ -3350,6 +3350,77 @@ int64_t ykhost_explain_message(ykhost_t* h, const char* allocation_key, int32_t 
   return ykhost_explain_format(h, bins, out, len);
 }
 
+// ---- how many copies of an ask the cluster still takes (ykpred_headroom) -----------------------------------------------------------
+// The allocation-phase lists always: the reservation lists carry no NodeResourcesFit, and without it nothing bounds the count.
+int32_t ykhost_headroom(ykhost_t* h, int32_t n, const int32_t* asks, int64_t* out_cells) {
+  YKHOST_LOCKED(h);
+  if (n < 0 || (n > 0 && !out_cells)) return fail(h, "headroom: bad argument", -1);
+  if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
+  int rc = sync(h);
+  if (rc) return rc;
+  const int P = (int)h->pending.size();
+  for (int i = 0; i < n; ++i)
+    if ((asks ? asks[i] : i) < 0 || (asks ? asks[i] : i) >= P) return fail(h, "headroom: ask index out of range", YKPRED_E_INVALID);
+  // An ask routed to the CPU manager gets status 1 without a device call; on a node-sharded handle every ask goes to the engine, as in
+  // ykhost_explain (the call is collective and the shards' dictionaries may route different asks).
+  int32_t world = 1;
+  ykpred_comm_info(h->eng, nullptr, &world, nullptr);
+  std::vector<int32_t> list, slot;
+  list.reserve((size_t)n);
+  slot.reserve((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const int row = asks ? asks[i] : i;
+    int64_t* c = out_cells + (size_t)i * YKPRED_HEADROOM_CELLS;
+    if (world <= 1 && h->enc.unsupported.count(h->pending[(size_t)row]->tpl)) {
+      std::fill(c, c + YKPRED_HEADROOM_CELLS, (int64_t)0);
+      c[3] = 1;
+    } else {
+      list.push_back(row);
+      slot.push_back(i);
+    }
+  }
+  if (list.empty() && world <= 1) return 0;
+  std::vector<int64_t> rows(list.size() * (size_t)YKPRED_HEADROOM_CELLS);
+  rc = ykpred_headroom(h->eng, (int32_t)list.size(), list.data(), h->alloc_pre, h->alloc_filt, rows.data());
+  if (rc) return fail(h, std::string("ykpred_headroom: ") + ykpred_last_error(h->eng), rc);
+  for (size_t k = 0; k < list.size(); ++k)
+    memcpy(out_cells + (size_t)slot[k] * YKPRED_HEADROOM_CELLS, rows.data() + k * YKPRED_HEADROOM_CELLS, YKPRED_HEADROOM_CELLS * sizeof(int64_t));
+  return 0;
+}
+
+int32_t ykhost_headroom_nodes(ykhost_t* h, int32_t pod, int32_t* out) {
+  YKHOST_LOCKED(h);
+  if (!out) return fail(h, "headroom_nodes: bad argument", -1);
+  if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
+  int rc = sync(h);
+  if (rc) return rc;
+  if (pod < 0 || pod >= (int)h->pending.size()) return fail(h, "headroom_nodes: ask index out of range", YKPRED_E_INVALID);
+  rc = ykpred_headroom_pod(h->eng, pod, h->alloc_pre, h->alloc_filt, out);
+  if (rc) return fail(h, std::string("ykpred_headroom_pod: ") + ykpred_last_error(h->eng), rc);
+  return 0;
+}
+
+// One ask named as the core names it (allocation key = pod UID): the figure for a task group, asked for one of its placeholders.
+int32_t ykhost_headroom_by_key(ykhost_t* h, const char* allocation_key, int64_t* out16) {
+  YKHOST_LOCKED(h);
+  if (!out16) return fail(h, "headroom_by_key: bad argument", -1);
+  std::fill(out16, out16 + YKPRED_HEADROOM_CELLS, (int64_t)0);
+  ensure_uid_index(h);
+  auto it = h->by_uid.find(allocation_key ? allocation_key : "");
+  if (it == h->by_uid.end()) return YKHOST_E_POD_NOT_FOUND;
+  if (!it->second->ask) return fail(h, "pod holds no ask row", YKHOST_E_NOT_AN_ASK);
+  if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
+  int rc = sync(h);
+  if (rc) return rc;
+  auto un = h->enc.unsupported.find(it->second->tpl);
+  if (un != h->enc.unsupported.end()) {
+    out16[3] = 1;
+    return fail(h, "ask is not evaluated by the engine (route it to the CPU predicate manager): " + un->second, YKHOST_E_UNSUPPORTED);
+  }
+  const int32_t row = it->second->row;
+  return ykhost_headroom(h, 1, &row, out16);
+}
+
 int32_t ykhost_pod_request_json(ykhost_t* h, int32_t pod, char* out, int32_t len) {
   YKHOST_LOCKED(h);
   if (pod < 0 || pod >= (int)h->pending.size()) return fail(h, "index out of range");

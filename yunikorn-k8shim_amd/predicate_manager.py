@@ -35,6 +35,11 @@ EVAL_SPREAD_COUNT_ONLY, EVAL_SPREAD_COUNTS_READY = 1 << 10, 1 << 11
 # [EXPLAIN_UNSUPPORTED] nodes not evaluated (routed ask), [EXPLAIN_REASON0 + b] reason bit b, [EXPLAIN_RESOURCE0 + r] insufficient resource r
 EXPLAIN_BINS = 32
 EXPLAIN_FIT, EXPLAIN_UNSUPPORTED, EXPLAIN_REASON0, EXPLAIN_RESOURCE0 = 9, 10, 12, 16
+# ykpred_headroom: int64[HEADROOM_CELLS] per ask — [HEADROOM_TOTAL] sum of replicas over the nodes, [HEADROOM_NODES] nodes taking at
+# least one copy, [HEADROOM_MAX] the most one node takes, [HEADROOM_STATUS] 0 computed / 1 routed ask / 2 coupled (total = max = -1),
+# nodes bound by [HEADROOM_BY_SLOTS] pod slots, [HEADROOM_BY_PORT] the host port, [HEADROOM_BY_RESOURCE0 + r] resource r
+HEADROOM_CELLS = 16
+HEADROOM_TOTAL, HEADROOM_NODES, HEADROOM_MAX, HEADROOM_STATUS, HEADROOM_BY_SLOTS, HEADROOM_BY_PORT, HEADROOM_BY_RESOURCE0 = 0, 1, 2, 3, 4, 5, 8
 
 
 def plugin_mask(names):
@@ -664,6 +669,43 @@ class GpuPredicateManager:
             buf = C.create_string_buffer(rc)
             self._check(self._L.ykhost_explain_message(self._h, uid.encode(), 1 if allocate else 0, buf, rc))
         return buf.value.decode()
+
+    # ---- how many copies of an ask still fit -----------------------------------------------------------------------
+    def headroom(self, pods=None, pre_mask=None, filt_mask=None):
+        """Per ask how many copies of it the cluster can still place, reduced on the device (ykpred_headroom): np.int64[n,
+        HEADROOM_CELLS]. pods: ask indices or UIDs in any order, repeats allowed; None = every ask. Always the allocation-phase
+        lists (the reservation lists carry no NodeResourcesFit); explicit masks go to ykpred_headroom directly, like query. Needs
+        no evaluation and disturbs none. A routed ask gets [HEADROOM_STATUS] = 1, a coupled one 2 with total = max = -1."""
+        if pods is None:
+            count, ptr = self.num_pods, None
+        else:
+            idx = [p if isinstance(p, (int, np.integer)) else self.pod_index(p) for p in pods]
+            arr = np.ascontiguousarray(idx, dtype=np.int32)
+            count, ptr = len(arr), arr.ctypes.data
+        out = np.zeros((max(count, 1), HEADROOM_CELLS), dtype=np.int64)
+        if pre_mask is None and filt_mask is None:
+            self._check(self._L.ykhost_headroom(self._h, count, ptr, out.ctypes.data))
+        else:
+            self.sync()
+            pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
+            if ptr is None:
+                arr = np.arange(count, dtype=np.int32)
+                ptr = arr.ctypes.data
+            self._pcheck(self._P.ykpred_headroom(self.engine, count, ptr, pre, filt, out.ctypes.data))
+        return out[:count].copy()
+
+    def headroom_nodes(self, pod, pre_mask=None, filt_mask=None):
+        """How many copies of ONE ask (index or UID) each node takes (ykpred_headroom_pod): np.int32[N]; -1 everywhere for a
+        coupled ask. On a node-sharded manager: this shard's nodes."""
+        p = pod if isinstance(pod, (int, np.integer)) else self.pod_index(pod)
+        out = np.zeros(max(self.num_nodes, 1), dtype=np.int32)
+        if pre_mask is None and filt_mask is None:
+            self._check(self._L.ykhost_headroom_nodes(self._h, int(p), out.ctypes.data))
+        else:
+            self.sync()
+            pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
+            self._pcheck(self._P.ykpred_headroom_pod(self.engine, int(p), pre, filt, out.ctypes.data))
+        return out[:self.num_nodes].copy()
 
     def round_info(self):
         """ykpred_get_round_info: how the allocation rounds so far were decided (in batches / by the sequential kernel)."""
