@@ -259,6 +259,31 @@ int32_t ykhost_headroom(ykhost_t* h, int32_t n, const int32_t* asks /* NULL = as
 int32_t ykhost_headroom_nodes(ykhost_t* h, int32_t pod, int32_t* out /* [N] */);
 int32_t ykhost_headroom_by_key(ykhost_t* h, const char* allocation_key, int64_t* out16 /* [16] */);
 
+/* Headroom per TOPOLOGY DOMAIN (ykpred.h: ykpred_headroom_groups) — which zone, rack or host still takes all minMember members of a gang
+ * with a locality requirement, and which of them is the tightest fit: the value a shim adds to the placeholders' nodeSelector. The groups
+ * are derived from a node LABEL KEY in the mirror: group ids are the ranks of the bytewise-sorted distinct values of the key, a node
+ * without the label is in no group (-1). The column is kept per (key, node-table epoch). Always the ALLOCATION-phase plugin lists.
+ *   ykhost_headroom_domains        syncs and makes ONE engine call for the listed asks (NULL = asks 0..n-1) with want[i] members each (NULL
+ *                                  = 1): out_summary[i] = the YKPRED_GROUP_SUMMARY cells; out_groups (may be NULL) [i][G + 1]
+ *                                  [YKPRED_GROUP_CELLS] = { copies, nodes } per domain, row G for the nodes without the label;
+ *                                  groups_cap = the int64 cells out_groups holds (YKPRED_E_INVALID when fewer than n * (G + 1) * 2).
+ *                                  → G >= 0, the number of domains, or an error < 0. A routed ask gets status 1 without a device call.
+ *                                  On a node-sharded handle the call is COLLECTIVE: the shards unite their value lists
+ *                                  (ykpred_comm_allgather_bytes, lengths first), so ids, rows and summaries are cluster-wide.
+ *                                  Every rank passes the same asks, wants, key and capacity: the engine's agreement step turns a
+ *                                  bad index or want on one rank into the same error on all of them.
+ *   ykhost_domain_values           the values of the key in id order as a JSON array → the length needed (with the terminator), as
+ *                                  ykhost_explain_format. Collective on a node-sharded handle for the same reason.
+ *   ykhost_headroom_domain_by_key  ONE crossing for one ask by allocation key (pod UID): the summary, and the domain with the most
+ *                                  copies / the tightest domain that holds `want` as label VALUES ("" when there is none). → 0, or the
+ *                                  errors of ykhost_headroom_by_key (YKHOST_E_UNSUPPORTED with out_summary[0] = 1). */
+int32_t ykhost_headroom_domains(ykhost_t* h, int32_t n, const int32_t* pods /* NULL = asks 0..n-1 */, const int64_t* want /* [n], NULL = all 1 */,
+                                const char* label_key, int64_t* out_summary /* [n][8] */, int64_t* out_groups /* [n][G + 1][2], may be NULL */,
+                                int64_t groups_cap);
+int64_t ykhost_domain_values(ykhost_t* h, const char* label_key, char* out, int64_t len);
+int32_t ykhost_headroom_domain_by_key(ykhost_t* h, const char* allocation_key, const char* label_key, int64_t want, int64_t* out_summary /* [8] */,
+                                      char* best, int64_t best_len, char* tightest, int64_t tightest_len);
+
 /* Engine calls that came back YKPRED_E_DEVICE / YKPRED_E_NOMEM so far (failed allocation, lost device). Each one marks the whole
  * device state stale: the failing call returns its error (Predicates() < 0: the Go manager routes the ask to the CPU predicate
  * manager — SURVEY.md §5, "must degrade, never fail scheduling"), the mirror stays intact, and the next ykhost_sync /

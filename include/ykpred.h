@@ -38,7 +38,8 @@
 extern "C" {
 #endif
 
-/* (ykpred_headroom + ykpred_headroom_pod + YKPRED_HEADROOM_CELLS arrived WITHIN version 4 as well, detected the same way:
+/* (ykpred_headroom_groups + YKPRED_GROUP_CELLS / YKPRED_GROUP_SUMMARY arrived WITHIN version 4 too: dlsym("ykpred_headroom_groups"))
+ * (ykpred_headroom + ykpred_headroom_pod + YKPRED_HEADROOM_CELLS arrived WITHIN version 4 as well, detected the same way:
  *    dlsym("ykpred_headroom"))
  * (ykpred_explain + YKPRED_EXPLAIN_BINS arrived WITHIN version 4, without a bump: a host that needs the call detects it by the
  *    exported symbol — dlsym("ykpred_explain") — not by the version number)
@@ -505,6 +506,45 @@ int32_t ykpred_headroom(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks 
  * cell for a coupled ask, 0 everywhere for a YKPRED_SPEC_UNSUPPORTED spec. On a node-sharded engine: this shard's nodes only, nothing
  * is exchanged. Errors as ykpred_query_pod, plus YKPRED_E_INVALID unless NodeResourcesFit is in both lists. */
 int32_t ykpred_headroom_pod(ykpred_engine_t* e, int32_t pod_index, uint32_t prefilter_plugins, uint32_t filter_plugins, int32_t* out /* [N] */);
+
+/* Headroom per TOPOLOGY DOMAIN — which zone, rack or host still takes the gang. node_group[n] in {-1, 0 .. num_groups-1} partitions the
+ * node table (-1: the node is in no group). For a listed ask a and a group g:
+ *   copies(a, g) = sum over the nodes n of group g of replicas(a, n)      (replicas: exactly ykpred_headroom's, the same device routine)
+ *   nodes(a, g)  = how many of those nodes have replicas(a, n) >= 1
+ * out_groups[i][g] = { copies, nodes } for g = 0 .. num_groups-1; row [num_groups] holds the same two figures for the ungrouped nodes.
+ * out_summary[i], for want[i] (NULL: every want is 1):
+ *  [0]      status, exactly cell [3] of ykpred_headroom: 0 computed, 1 routed, 2 coupled
+ *  [1]      groups with copies >= 1
+ *  [2]      groups with copies >= want
+ *  [3], [4] the group with the MOST copies and its copies; ties go to the lowest id; -1, 0 when [1] == 0
+ *  [5], [6] the TIGHTEST group that still holds want — the smallest copies >= want, ties to the lowest id — and its copies; -1, 0 when
+ *           [2] == 0
+ *  [7]      copies on ungrouped nodes
+ * Status 0, same ask and plugin lists: sum over g of copies + [7] == ykpred_headroom [0]; sum of nodes over every row == ykpred_headroom
+ *   [1]; [4] <= ykpred_headroom [0]. Status 2 (coupled): every copies cell and [7] are -1, [1] = [2] = [4] = 0, [3] = -1, [5], [6] = -1, 0;
+ *   the nodes cells still hold the single-copy fit count per group. Status 1 (routed): every other cell is 0.
+ * Everything else is ykpred_headroom's: the asks are reduced to their distinct (spec, NodeName) tasks and the summaries to the distinct
+ *   (task, want); any order, repeats allowed; the call reads the TABLES only, needs no evaluation and invalidates none; it prepares the
+ *   topology histograms as ykpred_query does; it counts as one query; roctx range "ykpred:headroom_groups"; n_asks == 0 returns YKPRED_OK;
+ *   a table of N == 0 nodes gives zero rows with [3] = [5] = -1. YKPRED_E_INVALID for a bad pointer, an ask index out of range,
+ *   num_groups < 1, a want < 1, a group id outside [-1, num_groups) (checked on the host before any launch), or NodeResourcesFit missing
+ *   from either list; YKPRED_E_STATE before the tables are uploaded. out_groups may be NULL: only the summaries come back.
+ * The table of all tasks can be large (num_groups == N: one group per host), so the engine works through the tasks in table chunks under
+ *   a scratch budget (256 MB; YKPRED_TUNE group_scratch_mb). Up to YKPRED_GROUP_LDS_MAX_GROUPS groups a workgroup accumulates in LDS,
+ *   above it straight in the global table (YKPRED_TUNE group_lds=0 forces the latter); every add is an integer add, so both give the
+ *   same cells.
+ * NODE-SHARDED engines: COLLECTIVE. node_group is THIS shard's column, the group ids are cluster-wide by the caller's contract. The
+ *   agreement all-gather of ykpred_headroom runs first and also covers num_groups, the wants and the scratch budget (a rank that cannot
+ *   run makes every rank return the same error); then one all-reduce SUM (int64) per table chunk, and the summaries are derived AFTER it:
+ *   every rank returns identical cluster-wide rows and summaries. */
+#define YKPRED_GROUP_CELLS 2             /* per (ask, group) int64: [0] copies, [1] nodes */
+#define YKPRED_GROUP_SUMMARY 8           /* per ask int64, see above */
+#define YKPRED_GROUP_LDS_MAX_GROUPS 63   /* the largest num_groups whose per-workgroup table fits the LDS budget (32 KiB) */
+int32_t ykpred_headroom_groups(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks /* host, ask indices, any order, repeats allowed */,
+                               const int64_t* want /* host, [n_asks], NULL = all 1 */, int32_t num_groups,
+                               const int32_t* node_group /* host, [N] */, uint32_t prefilter_plugins, uint32_t filter_plugins,
+                               int64_t* out_summary /* host, [n_asks][YKPRED_GROUP_SUMMARY] */,
+                               int64_t* out_groups /* host, [n_asks][num_groups + 1][YKPRED_GROUP_CELLS], may be NULL */);
 
 /* PreemptionPredicates (predicate_manager.go:141-179): victims are described by their request vectors, in order. */
 int32_t ykpred_preemption(ykpred_engine_t* e, int32_t pod_index, int32_t node_index, int32_t num_victims,

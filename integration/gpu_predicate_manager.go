@@ -481,6 +481,44 @@ func (m *gpuPredicateManager) Headroom(pod *v1.Pod) (total, nodes, most int64, o
 	}
 }
 
+// DomainHeadroom answers "which zone, rack or host still takes all `want` members of this gang" for a task group with a locality
+// requirement — the value a shim adds to the placeholders' nodeSelector before it waits for placeholderTimeoutInSeconds. The domains are
+// the values of labelKey among the mirrored nodes; the engine sums Headroom's per-node copies per domain on the device
+// (ykpred_headroom_groups). fits = how many domains hold at least `want` copies, tightest = the one with the fewest copies that still
+// holds them (ties: the bytewise smallest value) with its copies, most = the domain with the most copies with its copies. ONE crossing:
+// ykhost_headroom_domain_by_key looks the ask up by allocation key and hands both domains back as label values. The figures are upper
+// bounds while other groups compete for the same nodes. ok == false when the pod is not a mirrored ask, is routed to the CPU predicate
+// manager, the engine failed, or the ask is COUPLED — the caller then places the gang as it does today.
+func (m *gpuPredicateManager) DomainHeadroom(pod *v1.Pod, labelKey string, want int64) (fits int64, tightest string, tightestCopies int64, most string, mostCopies int64, ok bool) {
+	if pod == nil || want < 1 {
+		return 0, "", 0, "", 0, false
+	}
+	var cells [8]C.int64_t
+	var best, tight [256]C.char
+	uid := C.CString(string(pod.UID))
+	key := C.CString(labelKey)
+	rc := C.ykhost_headroom_domain_by_key(m.host, uid, key, C.int64_t(want), &cells[0], &best[0], 256, &tight[0], 256)
+	C.free(unsafe.Pointer(uid))
+	C.free(unsafe.Pointer(key))
+	switch {
+	case rc == 0 && cells[0] == 0:
+		return int64(cells[2]), C.GoString(&tight[0]), int64(cells[6]), C.GoString(&best[0]), int64(cells[4]), true
+	case rc == 0:
+		return 0, "", 0, "", 0, false
+	case rc == C.YKHOST_E_UNSUPPORTED:
+		m.Counters.RoutedUnsupported.Add(1)
+		return 0, "", 0, "", 0, false
+	case rc == C.YKHOST_E_POD_NOT_FOUND || rc == C.YKHOST_E_NOT_AN_ASK:
+		m.Counters.RoutedNotMirrored.Add(1)
+		return 0, "", 0, "", 0, false
+	default:
+		m.Counters.RoutedOnError.Add(1)
+		log.Log(log.ShimPredicates).Warn("GPU predicate engine error, no per-domain headroom for the ask",
+			zap.String("error", C.GoString(C.ykhost_last_error(m.host))))
+		return 0, "", 0, "", 0, false
+	}
+}
+
 // ResidentStats: Predicates() calls answered from the mirrored resident answer, per pair because the node's column changed,
 // by whole-ask device queries, and the answer / failing-plugin fetches behind them.
 func (m *gpuPredicateManager) ResidentStats() (resident, dirtyColumn, query, answerFetches, codeFetches int64) {

@@ -137,6 +137,8 @@ def load_ykpred():
     L.ykpred_explain.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     L.ykpred_headroom.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     L.ykpred_headroom_pod.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.ykpred_headroom_groups.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                         C.c_void_p, C.c_void_p]
     _pred = L
     return L
 
@@ -213,6 +215,11 @@ def load_ykhost():
     L.ykhost_headroom.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.ykhost_headroom_nodes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     L.ykhost_headroom_by_key.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
+    L.ykhost_headroom_domains.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64]
+    L.ykhost_domain_values.restype = C.c_int64
+    L.ykhost_domain_values.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int64]
+    L.ykhost_headroom_domain_by_key.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_char_p, C.c_int64,
+                                                C.c_char_p, C.c_int64]
     L.ykhost_device_errors.restype = C.c_int64
     L.ykhost_device_errors.argtypes = [C.c_void_p]
     _host = L

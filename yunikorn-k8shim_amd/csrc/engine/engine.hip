@@ -16,6 +16,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <map>
 #include <unordered_map>
 #include <vector>
 
@@ -275,6 +276,7 @@ struct ykpred_engine {
   DevBuf d_agree;  // sharded rounds: what the ranks agree on before the first batch
   DevBuf d_explain;  // ykpred_explain: task specs | task pins | [tasks][YKPRED_EXPLAIN_BINS] counts
   DevBuf d_headroom;  // ykpred_headroom: [tasks][YKPRED_HEADROOM_CELLS] cells | [tasks] max replicas | task specs | task pins
+  DevBuf d_groups;  // ykpred_headroom_groups: summaries | pair wants | pair tasks | task specs | task pins | coupled | node groups | one table chunk
   DevBuf d_bytes_gather;  // ykpred_comm_allgather_bytes
   DevBuf d_topo_agree;  // node-sharded: the shape of every rank's topology histograms (agree_topology)
   u64 dict_digest = 0;  // ykpred_set_dictionary_digest
@@ -345,6 +347,9 @@ struct ykpred_engine {
   int combine_slices = 1;           // combine_slices: 0 = index-row populations take the wave-per-chunk writer instead of k_walk_rows
   int decide_groups_from = 16384;   // decide_groups_from: classes from which k_decide serves four classes per wave
   int early_counts = 1;             // early_counts: 0 = class counts by the writers and the per-ask scatter behind them (the round-4 order)
+  int group_lds = -1;               // group_lds: k_headroom_groups accumulates in LDS (1, wherever the chunk's table fits kGroupLdsBytes) or straight in the global table (0); -1 = LDS wherever it fits
+  int group_scratch_mb = 256;       // group_scratch_mb: the budget of one table chunk of ykpred_headroom_groups (0 = one task per chunk)
+  int group_chunk_tasks = 0;        // group_chunk_tasks: tasks per table chunk whatever the budget says (0 = from the budget): several chunks on a small table
   int max_lds_bytes = 64 * 1024;   // opt-in dynamic LDS limit of the device (hipDeviceAttributeMaxSharedMemoryPerBlock)
   int num_cus = 256;               // compute units of the device (hipDeviceAttributeMultiprocessorCount)
   int n_bands = 0, n_band_steps = 0, n_classes_a = 0, n_fix_rows = 0;
@@ -1706,6 +1711,9 @@ int32_t ykpred_create(const ykpred_config_t* cfg, ykpred_engine_t** out) {
       else if (key == "fuse_wpl") e->fuse_wpl = val;
       else if (key == "fuse_combine") e->fuse_combine = val;
       else if (key == "class_runs_min_rows") e->class_runs_min_rows = std::max(val, 1);
+      else if (key == "group_lds") e->group_lds = val;
+      else if (key == "group_scratch_mb") e->group_scratch_mb = std::max(val, 0);
+      else if (key == "group_chunk_tasks") e->group_chunk_tasks = std::max(val, 0);
       else {
         g_create_error = "YKPRED_TUNE: unknown key '" + key + "'";
         delete e;
@@ -4540,29 +4548,34 @@ static bool headroom_coupled(const ykpred_engine* e, int32_t spec, uint32_t pre,
   return (spread_en || ipa_en) && (size_t)spec < e->spec_sig_spread.size() && e->spec_sig_spread[(size_t)spec] >= 0;
 }
 
-// How many copies of an ask the cluster still takes: per listed ask the per-node replicas (kernels.hip.h: replicas) reduced over every
-// node on the device (k_headroom). The shape of ykpred_explain — tasks, agreement, one reduce — with an int64 table and a max beside it.
-int32_t ykpred_headroom(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, uint32_t pre, uint32_t filt, int64_t* out) {
-  YK_SERIALISE(e);
-  Range roctx_range("ykpred:headroom");
-  if (e) e->n_queries++;
-  static_assert(ykk::kHeadroomCells == YKPRED_HEADROOM_CELLS, "k_headroom writes the layout of ykpred.h");
-  constexpr size_t B = YKPRED_HEADROOM_CELLS;
-  if (!e) return YKPRED_E_INVALID;
+// What ykpred_headroom and ykpred_headroom_groups share in front of their kernels: the argument checks, the TASKS of the list, the
+// topology histograms, and — on a node-sharded engine — the agreement all-gather.
+extern "C++" {  // (a template: the surrounding block has C linkage)
+struct HeadroomTasks {
+  std::vector<int32_t> task_of, spec, pin;  // ask i of the list → its task; per task the spec and the NodeName pin
+};
+// `more_checks` (a callable) runs after the common checks passed and returns a status of the call's own with its text; `more` is a
+// hash of whatever else the ranks of a sharded engine must hold alike. *run == false on return: the caller returns the status at once
+// (an error on some rank, or n_asks == 0).
+template <class MoreChecks>
+static int32_t headroom_prepare(ykpred_engine* e, const std::string& name, int32_t n_asks, const int32_t* asks, bool pointers_ok, uint32_t pre,
+                                uint32_t filt, MoreChecks more_checks, u64 more, HeadroomTasks* tasks, bool* run) {
+  *run = false;
   const bool sharded = e->comm && e->comm_world > 1;
   int rc = YKPRED_OK;
-  const char* why = "";
-  if (n_asks < 0 || (n_asks > 0 && (!asks || !out))) rc = YKPRED_E_INVALID, why = "headroom: bad argument";
-  else if (!(pre & filt & YKPRED_PLUGIN_NODE_RESOURCES_FIT)) rc = YKPRED_E_INVALID, why = "headroom: NodeResourcesFit must be in both plugin lists (nothing else bounds the count)";
-  else if (!e->nodes_set || !e->specs_set || !e->pods_set) rc = YKPRED_E_STATE, why = "headroom: tables not uploaded";
+  std::string why;
+  if (n_asks < 0 || !pointers_ok) rc = YKPRED_E_INVALID, why = name + ": bad argument";
+  else if (!(pre & filt & YKPRED_PLUGIN_NODE_RESOURCES_FIT)) rc = YKPRED_E_INVALID, why = name + ": NodeResourcesFit must be in both plugin lists (nothing else bounds the count)";
+  else if (!e->nodes_set || !e->specs_set || !e->pods_set) rc = YKPRED_E_STATE, why = name + ": tables not uploaded";
   else
     for (int i = 0; i < n_asks; ++i)
-      if (asks[i] < 0 || asks[i] >= e->P) rc = YKPRED_E_INVALID, why = "headroom: index out of range";
+      if (asks[i] < 0 || asks[i] >= e->P) rc = YKPRED_E_INVALID, why = name + ": index out of range";
+  if (rc == YKPRED_OK) rc = more_checks(&why);
   if (!sharded && rc != YKPRED_OK) return fail(e, rc, why);
   if (!sharded && n_asks == 0) return YKPRED_OK;
   // Tasks: the distinct (spec, pin) of the list, keyed as ykpred_explain keys them (a sharded engine cannot key on the pin, a node index
   // of ITS shard; with by_ask every distinct ask index is a task — the keys every rank derives alike).
-  std::vector<int32_t> task_of, t_spec, t_pin;
+  std::vector<int32_t>&task_of = tasks->task_of, &t_spec = tasks->spec, &t_pin = tasks->pin;
   auto build_tasks = [&](bool by_ask) {
     std::unordered_map<u64, int32_t> index;
     task_of.assign((size_t)n_asks, 0);
@@ -4584,18 +4597,19 @@ int32_t ykpred_headroom(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks,
   HIPCHK(hipSetDevice(e->cfg.device));
   hipStream_t st = e->own_stream;
   if (rc == YKPRED_OK && e->N > 0 && n_asks > 0) {
-    // (the histogram preparation of ykpred_query: a coupled ask's fit count [1] reads them)
+    // (the histogram preparation of ykpred_query: a coupled ask's fit count reads them)
     if ((pre & filt & (YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD | YKPRED_PLUGIN_INTER_POD_AFFINITY))) rc = ensure_histograms(e, st);
     else if (e->spread_dirty) rc = build_spread_tables(e, st);
     if (rc != YKPRED_OK && !sharded) return rc;
   }
   if (sharded) {
-    // Collective: (status, ask count, list, task partition) agreed before anybody enters the reduces, as in ykpred_explain.
+    // Collective: (status, ask count, list, task partition, the call's own hash) agreed before anybody enters the reduces, as in
+    // ykpred_explain.
     struct Agree {
       int32_t rc, n;
-      u64 list, partition;
+      u64 list, partition, more;
     };
-    Agree mine{rc, n_asks, 0x9e3779b97f4a7c15ull, 0x9e3779b97f4a7c15ull};
+    Agree mine{rc, n_asks, 0x9e3779b97f4a7c15ull, 0x9e3779b97f4a7c15ull, more};
     if (rc == YKPRED_OK)
       for (int i = 0; i < n_asks; ++i) {
         mine.list = (mine.list ^ (u64)(uint32_t)asks[i]) * 0x100000001b3ull;
@@ -4611,17 +4625,41 @@ int32_t ykpred_headroom(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks,
     HIPCHK(hipStreamSynchronize(st));
     for (int g = 0; g < W; ++g)
       if (all[(size_t)g].rc != YKPRED_OK)
-        return fail(e, all[(size_t)g].rc, "headroom (sharded): rank " + std::to_string(g) + " cannot run the call (" +
-                                              (g == e->comm_rank && *why ? why : "bad argument, NodeResourcesFit missing from a list, tables not uploaded, an index out of range or stale topology histograms") +
+        return fail(e, all[(size_t)g].rc, name + " (sharded): rank " + std::to_string(g) + " cannot run the call (" +
+                                              (g == e->comm_rank && !why.empty() ? why : "bad argument, NodeResourcesFit missing from a list, tables not uploaded, an index out of range or stale topology histograms") +
                                               "): no rank runs it");
     for (int g = 0; g < W; ++g)
       if (all[(size_t)g].n != all[0].n || all[(size_t)g].list != all[0].list)
-        return fail(e, YKPRED_E_INVALID, "headroom (sharded): rank " + std::to_string(g) + " was handed a different ask list: every rank passes the same asks");
+        return fail(e, YKPRED_E_INVALID, name + " (sharded): rank " + std::to_string(g) + " was handed a different ask list: every rank passes the same asks");
+    for (int g = 0; g < W; ++g)
+      if (all[(size_t)g].more != all[0].more)
+        return fail(e, YKPRED_E_INVALID, name + " (sharded): rank " + std::to_string(g) + " was handed different arguments beside the ask list: every rank passes the same");
     if (n_asks == 0) return YKPRED_OK;
     bool same = true;
     for (int g = 0; g < W; ++g) same = same && all[(size_t)g].partition == all[0].partition;
     if (!same) build_tasks(true);
   }
+  *run = true;
+  return YKPRED_OK;
+}
+}  // extern "C++"
+
+// How many copies of an ask the cluster still takes: per listed ask the per-node replicas (kernels.hip.h: replicas) reduced over every
+// node on the device (k_headroom). The shape of ykpred_explain — tasks, agreement, one reduce — with an int64 table and a max beside it.
+int32_t ykpred_headroom(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, uint32_t pre, uint32_t filt, int64_t* out) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:headroom");
+  if (e) e->n_queries++;
+  static_assert(ykk::kHeadroomCells == YKPRED_HEADROOM_CELLS, "k_headroom writes the layout of ykpred.h");
+  constexpr size_t B = YKPRED_HEADROOM_CELLS;
+  if (!e) return YKPRED_E_INVALID;
+  HeadroomTasks tasks;
+  bool run = false;
+  const int32_t rc = headroom_prepare(e, "headroom", n_asks, asks, n_asks <= 0 || (asks && out), pre, filt, [](std::string*) { return (int)YKPRED_OK; }, 0, &tasks, &run);
+  if (!run) return rc;
+  const bool sharded = e->comm && e->comm_world > 1;
+  const std::vector<int32_t>&task_of = tasks.task_of, &t_spec = tasks.spec, &t_pin = tasks.pin;
+  hipStream_t st = e->own_stream;
   const size_t T = t_spec.size();
   HIPCHK(e->d_headroom.ensure(T * ((B + 1) * sizeof(int64_t) + 2 * sizeof(int32_t)) + 64));
   int64_t* d_cells = e->d_headroom.as<int64_t>();  // (the table and the max first: what the reduces and the copy move)
@@ -4688,6 +4726,143 @@ int32_t ykpred_headroom_pod(ykpred_engine_t* e, int32_t pod, uint32_t pre, uint3
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, e->d_scratch.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
+  return YKPRED_OK;
+}
+
+// Headroom per GROUP of nodes (a zone, a rack, a host): the replicas of ykpred_headroom summed per group id of a caller-given column
+// (k_headroom_groups), and per (ask, want) which group holds the most copies and which is the tightest that still holds want
+// (k_group_summary). The [tasks][G + 1][2] table can be large (G == N: the hostname case), so the tasks are worked through in TABLE CHUNKS
+// under a scratch budget: fill, kernel, (all-reduce), summary, copy back. The chunk size follows from the budget, G and the task count
+// alone — values every rank of a sharded engine holds alike (the agreement covers them).
+int32_t ykpred_headroom_groups(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, const int64_t* want, int32_t num_groups,
+                               const int32_t* node_group, uint32_t pre, uint32_t filt, int64_t* out_summary, int64_t* out_groups) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:headroom_groups");
+  if (e) e->n_queries++;
+  static_assert(ykk::kGroupCells == YKPRED_GROUP_CELLS && ykk::kGroupSummary == YKPRED_GROUP_SUMMARY, "the kernels write the layout of ykpred.h");
+  static_assert(ykk::kGroupLdsMaxGroups == YKPRED_GROUP_LDS_MAX_GROUPS, "ykpred.h names the largest G of the LDS form");
+  if (!e) return YKPRED_E_INVALID;
+  constexpr size_t S = YKPRED_GROUP_SUMMARY;
+  const int G = num_groups;
+  auto more_checks = [&](std::string* why) -> int {
+    if (n_asks == 0) return YKPRED_OK;
+    if (G < 1 || G > (1 << 28)) return *why = "headroom_groups: num_groups must be 1 .. 2^28", YKPRED_E_INVALID;
+    if (e->N > 0 && !node_group) return *why = "headroom_groups: bad argument", YKPRED_E_INVALID;
+    if (want)
+      for (int i = 0; i < n_asks; ++i)
+        if (want[i] < 1) return *why = "headroom_groups: want must be at least 1", YKPRED_E_INVALID;
+    for (int n = 0; n < e->N; ++n)
+      if (node_group[n] < -1 || node_group[n] >= G) return *why = "headroom_groups: group id of node " + std::to_string(n) + " outside [-1, num_groups)", YKPRED_E_INVALID;
+    return YKPRED_OK;
+  };
+  u64 more = 0x9e3779b97f4a7c15ull;
+  more = (more ^ (u64)(uint32_t)G) * 0x100000001b3ull;
+  more = (more ^ (u64)(uint32_t)e->group_scratch_mb) * 0x100000001b3ull;
+  more = (more ^ (u64)(uint32_t)e->group_chunk_tasks) * 0x100000001b3ull;
+  if (n_asks > 0 && asks && out_summary)
+    for (int i = 0; i < n_asks; ++i) more = (more ^ (u64)(want ? want[i] : 1)) * 0x100000001b3ull;
+  HeadroomTasks tasks;
+  bool run = false;
+  const int32_t rc = headroom_prepare(e, "headroom_groups", n_asks, asks, n_asks <= 0 || (asks && out_summary), pre, filt, more_checks, more, &tasks, &run);
+  if (!run) return rc;
+  const bool sharded = e->comm && e->comm_world > 1;
+  hipStream_t st = e->own_stream;
+  const size_t T = tasks.spec.size(), N = (size_t)e->N, row_cells = ((size_t)G + 1) * YKPRED_GROUP_CELLS;
+  // the distinct (task, want) pairs, in (task, want) order: the pairs of one table chunk are a range
+  std::map<std::pair<int32_t, int64_t>, int32_t> pair_index;
+  for (int i = 0; i < n_asks; ++i) pair_index.emplace(std::make_pair(tasks.task_of[(size_t)i], want ? want[i] : (int64_t)1), 0);
+  std::vector<int32_t> pair_task;
+  std::vector<int64_t> pair_want;
+  for (auto& kv : pair_index) {
+    kv.second = (int32_t)pair_task.size();
+    pair_task.push_back(kv.first.first);
+    pair_want.push_back(kv.first.second);
+  }
+  const size_t NP = pair_task.size();
+  std::vector<int32_t> coupled(T);
+  for (size_t k = 0; k < T; ++k) coupled[k] = headroom_coupled(e, tasks.spec[k], pre, filt) ? 1 : 0;
+  // table chunks
+  const size_t task_bytes = (row_cells + 1) * sizeof(int64_t);  // a task's rows and its `unsupported` cell
+  size_t Tc = std::max<size_t>(1, ((size_t)e->group_scratch_mb << 20) / task_bytes);
+  if (Tc >= (size_t)ykk::kExplainTasks) Tc -= Tc % (size_t)ykk::kExplainTasks;
+  if (e->group_chunk_tasks > 0) Tc = (size_t)e->group_chunk_tasks;
+  Tc = std::min(Tc, T);
+  auto up8 = [](size_t b) { return (b + 7) & ~(size_t)7; };
+  const size_t o_want = NP * S * sizeof(int64_t), o_ptask = o_want + NP * sizeof(int64_t), o_spec = up8(o_ptask + NP * sizeof(int32_t)),
+               o_pin = o_spec + T * sizeof(int32_t), o_coupled = o_pin + T * sizeof(int32_t), o_group = o_coupled + T * sizeof(int32_t),
+               o_table = up8(o_group + N * sizeof(int32_t));
+  HIPCHK(e->d_groups.ensure(o_table + Tc * task_bytes + 64));
+  char* base = e->d_groups.as<char>();
+  int64_t* d_summary = (int64_t*)base;
+  int64_t* d_pwant = (int64_t*)(base + o_want);
+  int32_t* d_ptask = (int32_t*)(base + o_ptask);
+  int32_t* d_spec = (int32_t*)(base + o_spec);
+  int32_t* d_pin = (int32_t*)(base + o_pin);
+  int32_t* d_coupled = (int32_t*)(base + o_coupled);
+  int32_t* d_group = (int32_t*)(base + o_group);
+  int64_t* d_table = (int64_t*)(base + o_table);
+  std::vector<int32_t> pair_local(NP);  // (the summary kernel indexes the chunk)
+  for (size_t p = 0; p < NP; ++p) pair_local[p] = (int32_t)((size_t)pair_task[p] % Tc);
+  HIPCHK(hipMemcpyAsync(d_pwant, pair_want.data(), NP * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_ptask, pair_local.data(), NP * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_spec, tasks.spec.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_pin, tasks.pin.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_coupled, coupled.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  if (N > 0) HIPCHK(hipMemcpyAsync(d_group, node_group, N * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  const bool lds = G <= ykk::kGroupLdsMaxGroups && e->group_lds != 0;
+  // asks by task (a counting sort): the rows of a chunk go to every ask of its tasks
+  std::vector<int32_t> ask_begin, ask_list;
+  std::vector<int64_t> rows;
+  if (out_groups) {
+    ask_begin.assign(T + 1, 0);
+    for (int i = 0; i < n_asks; ++i) ask_begin[(size_t)tasks.task_of[(size_t)i] + 1]++;
+    for (size_t k = 0; k < T; ++k) ask_begin[k + 1] += ask_begin[k];
+    ask_list.resize((size_t)n_asks);
+    std::vector<int32_t> at(ask_begin.begin(), ask_begin.end() - 1);
+    for (int i = 0; i < n_asks; ++i) ask_list[(size_t)at[(size_t)tasks.task_of[(size_t)i]]++] = i;
+    rows.resize(Tc * row_cells);
+  }
+  size_t p_lo = 0;
+  for (size_t c0 = 0; c0 < T; c0 += Tc) {
+    const size_t tc = std::min(Tc, T - c0);
+    int64_t* d_unsupported = d_table + tc * row_cells;
+    HIPCHK(hipMemsetAsync(d_table, 0, tc * task_bytes, st));
+    if (N > 0) {
+      const dim3 grid((unsigned)((tc + ykk::kExplainTasks - 1) / ykk::kExplainTasks), (unsigned)((N + ykk::kBlock - 1) / ykk::kBlock));
+      const size_t shmem = lds ? (size_t)ykk::kExplainTasks * row_cells * sizeof(int64_t) : 0;
+      if (lds)
+        hipLaunchKernelGGL(ykk::k_headroom_groups<true>, grid, dim3(ykk::kBlock), shmem, st, node_table(e), spec_table(e), (int)tc, d_spec + c0,
+                           d_pin + c0, pre, filt, d_group, G, (ykk::i64*)d_table, (ykk::i64*)d_unsupported);
+      else
+        hipLaunchKernelGGL(ykk::k_headroom_groups<false>, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e), (int)tc, d_spec + c0,
+                           d_pin + c0, pre, filt, d_group, G, (ykk::i64*)d_table, (ykk::i64*)d_unsupported);
+      HIPCHK(hipGetLastError());
+    }
+    if (sharded) NCCLCHK(rccl()->AllReduce(d_table, d_table, tc * (row_cells + 1), ncclInt64, ncclSum, e->comm, st));
+    size_t p_hi = p_lo;
+    while (p_hi < NP && (size_t)pair_task[p_hi] < c0 + tc) ++p_hi;
+    if (p_hi > p_lo) {
+      hipLaunchKernelGGL(ykk::k_group_summary, dim3((unsigned)((p_hi - p_lo + ykk::kWavesPerBlock - 1) / ykk::kWavesPerBlock)), dim3(ykk::kBlock), 0, st,
+                         (int)(p_hi - p_lo), d_ptask + p_lo, (const ykk::i64*)(d_pwant + p_lo), G, (ykk::i64*)d_table,
+                         (const ykk::i64*)d_unsupported, d_coupled + c0, (ykk::i64*)(d_summary + p_lo * S));
+      HIPCHK(hipGetLastError());
+    }
+    p_lo = p_hi;
+    if (out_groups) {
+      HIPCHK(hipMemcpyAsync(rows.data(), d_table, tc * row_cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      for (size_t k = c0; k < c0 + tc; ++k)
+        for (int32_t j = ask_begin[k]; j < ask_begin[k + 1]; ++j)
+          memcpy(out_groups + (size_t)ask_list[(size_t)j] * row_cells, rows.data() + (k - c0) * row_cells, row_cells * sizeof(int64_t));
+    }
+  }
+  std::vector<int64_t> summaries(NP * S);
+  HIPCHK(hipMemcpyAsync(summaries.data(), d_summary, NP * S * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int i = 0; i < n_asks; ++i) {
+    const int32_t pr = pair_index.at(std::make_pair(tasks.task_of[(size_t)i], want ? want[i] : (int64_t)1));
+    memcpy(out_summary + (size_t)i * S, summaries.data() + (size_t)pr * S, S * sizeof(int64_t));
+  }
   return YKPRED_OK;
 }
 

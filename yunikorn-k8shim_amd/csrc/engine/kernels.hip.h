@@ -3057,6 +3057,125 @@ __global__ __launch_bounds__(kBlock) void k_headroom_pod(NodeTable t, SpecTable 
   out[n] = replicas(s, spec, pin, n, nr, (i64)t.allowed[n] - (i64)t.count[n], pre_mask, filt_mask, &binder);
 }
 
+// ykpred_headroom_groups: replicas summed per GROUP of nodes (a zone, a rack, a host): table[task][g][0] = Σ replicas over the nodes of
+// group g, [g][1] = how many of them take at least one copy; row G holds the nodes of no group (node_group[n] < 0). Grid and walk of
+// k_headroom: blockIdx.x = chunk of kExplainTasks tasks, blockIdx.y = 256 nodes, lane = node; the node columns and the lane's group id
+// are loaded once per chunk, the task data is wave-uniform, a wave in which no lane fits skips the task. Two accumulation forms:
+//   use_lds  (a template parameter: two kernels, told apart in a trace) the chunk's [kExplainTasks][G + 1][2] table lives in dynamic
+//            LDS (G <= kGroupLdsMaxGroups): lanes add into LDS, the block flushes its non-zero cells with one global integer add each;
+//   else     (up to G == N, where nearly every lane owns its cell) the adds go straight to the global table.
+// A wave-level merge of lanes that share a group id was measured and did not pay: every fitting lane adds for itself.
+// Every add is an integer add: the result does not depend on the order of arrival. unsupported[task] = 1 for a spec the engine does not
+// evaluate (written by the first node group alone; every cell of such a task stays 0: eval_pair rejects every pair).
+constexpr int kGroupCells = 2;
+constexpr int kGroupSummary = 8;
+constexpr int kGroupLdsBytes = 32 * 1024;  // LDS budget of the few-groups form: five workgroups still share a CU's 160 KiB
+constexpr int kGroupLdsMaxGroups = kGroupLdsBytes / (kExplainTasks * kGroupCells * (int)sizeof(i64)) - 1;
+template <bool use_lds>
+__global__ __launch_bounds__(kBlock) void k_headroom_groups(NodeTable t, SpecTable s, int n_tasks, const int* __restrict__ task_spec,
+                                                            const int* __restrict__ task_pin, unsigned pre_mask, unsigned filt_mask,
+                                                            const int* __restrict__ node_group, int G,
+                                                            i64* __restrict__ table, i64* __restrict__ unsupported) {
+  extern __shared__ i64 gacc[];  // use_lds: [kExplainTasks][G + 1][kGroupCells], the layout of the global table
+  const int row_cells = (G + 1) * kGroupCells;
+  const int k0 = blockIdx.x * kExplainTasks, kend = min(k0 + kExplainTasks, n_tasks);
+  if (use_lds) {
+    for (int i = threadIdx.x; i < (kend - k0) * row_cells; i += kBlock) gacc[i] = 0;
+    __syncthreads();
+  }
+  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+  int n = (blockIdx.y * kWavesPerBlock + wave) * kWave + lane;
+  const bool live = n < t.n;
+  if (!live) n = -1;
+  if (__ballot(live)) {  // (wave-uniform: a wave wholly past N skips the walk, not the barriers)
+    NodeRegs nr;
+    load_node(t, n, &nr);
+    const i64 slots = live ? (i64)t.allowed[n] - (i64)t.count[n] : 0;
+    int g = live ? node_group[n] : -1;
+    if (g < 0) g = G;
+    for (int k = k0; k < kend; ++k) {
+      int binder = 0;
+      const int rep = live ? replicas(s, task_spec[k], task_pin[k], n, nr, slots, pre_mask, filt_mask, &binder) : 0;
+      if (!__ballot(rep > 0)) continue;  // (wave-uniform: no lane fits)
+      if (rep <= 0) continue;
+      if (use_lds) {
+        i64* cell = gacc + (k - k0) * row_cells + g * kGroupCells;
+        atomicAdd((u64*)&cell[0], (u64)rep);
+        atomicAdd((u64*)&cell[1], (u64)1);
+      } else {
+        i64* cell = table + (size_t)k * row_cells + g * kGroupCells;
+        atomicAdd((u64*)&cell[0], (u64)rep);
+        atomicAdd((u64*)&cell[1], (u64)1);
+      }
+    }
+  }
+  if (use_lds) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < (kend - k0) * row_cells; i += kBlock) {
+      const i64 v = gacc[i];
+      if (v) atomicAdd((u64*)&table[(size_t)k0 * row_cells + i], (u64)v);
+    }
+  }
+  if (blockIdx.y == 0 && (int)threadIdx.x < kend - k0 && (s.flags[task_spec[k0 + threadIdx.x]] & kSpecUnsupported)) unsupported[k0 + threadIdx.x] = 1;
+}
+
+// The summary of one (task, want) over that task's G group rows, one wave per pair, after the table is complete (on a sharded engine:
+// after the all-reduce, so every rank derives the same cluster-wide summary). out[8]: [0] status, [1] groups with copies >= 1, [2] groups
+// with copies >= want, [3], [4] the group with the MOST copies and its copies (arg-max on (copies, -id): ties go to the lowest id; -1, 0
+// when no group takes a copy), [5], [6] the TIGHTEST group that still holds want (arg-min over copies >= want on (copies, id); -1, 0 when
+// none does), [7] the copies on ungrouped nodes. Lane l scans groups l, l + 64, ... in ascending order, then the lanes meet in a butterfly
+// whose comparison is total: deterministic. A task no shard evaluates (unsupported != 0) gets status 1 and zeros, its table row is zeroed;
+// a COUPLED task (the host says which) gets status 2, every copies cell of its row — ungrouped included — becomes -1 and the nodes cells
+// stay: the single-copy fit count per group. Pairs of one task write the same values into its row and read none of them.
+__global__ __launch_bounds__(kBlock) void k_group_summary(int n_pairs, const int* __restrict__ pair_task, const i64* __restrict__ pair_want, int G,
+                                                          i64* __restrict__ table, const i64* __restrict__ unsupported,
+                                                          const int* __restrict__ coupled, i64* __restrict__ summary) {
+  const int lane = threadIdx.x % kWave, p = blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
+  if (p >= n_pairs) return;  // (wave-uniform, no barrier below)
+  const int task = pair_task[p];
+  const i64 want = pair_want[p];
+  i64* row = table + (size_t)task * (G + 1) * kGroupCells;
+  i64* out = summary + (size_t)p * kGroupSummary;
+  if (unsupported[task] != 0) {
+    for (int i = lane; i < (G + 1) * kGroupCells; i += kWave) row[i] = 0;
+    if (lane < kGroupSummary) out[lane] = lane == 0 ? 1 : 0;
+    return;
+  }
+  if (coupled[task]) {
+    for (int g = lane; g <= G; g += kWave) row[g * kGroupCells] = -1;
+    if (lane < kGroupSummary) out[lane] = lane == 0 ? 2 : (lane == 3 || lane == 5 || lane == 7) ? -1 : 0;
+    return;
+  }
+  int some = 0, enough = 0, bg = -1, tg = -1;
+  i64 bc = 0, tc = 0x7fffffffffffffffll;
+  for (int g = lane; g < G; g += kWave) {
+    const i64 c = row[g * kGroupCells];
+    some += c >= 1;
+    enough += c >= want;
+    if (c > bc) bc = c, bg = g;
+    if (c >= want && c < tc) tc = c, tg = g;
+  }
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) {
+    some += __shfl_xor(some, off, kWave);
+    enough += __shfl_xor(enough, off, kWave);
+    const i64 obc = (i64)__shfl_xor((long long)bc, off, kWave), otc = (i64)__shfl_xor((long long)tc, off, kWave);
+    const int obg = __shfl_xor(bg, off, kWave), otg = __shfl_xor(tg, off, kWave);
+    if (obg >= 0 && (bg < 0 || obc > bc || (obc == bc && obg < bg))) bc = obc, bg = obg;
+    if (otg >= 0 && (tg < 0 || otc < tc || (otc == tc && otg < tg))) tc = otc, tg = otg;
+  }
+  if (lane == 0) {
+    out[0] = 0;
+    out[1] = some;
+    out[2] = enough;
+    out[3] = bg;
+    out[4] = bg < 0 ? 0 : bc;
+    out[5] = tg;
+    out[6] = tg < 0 ? 0 : tc;
+    out[7] = row[G * kGroupCells];
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // incremental column patch: only the bitmap columns of the listed (updated) nodes are re-evaluated
 // ---------------------------------------------------------------------------------------------------

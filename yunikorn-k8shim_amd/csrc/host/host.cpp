@@ -240,6 +240,18 @@ struct ykhost {
   // new requirement bit is then computed per DISTINCT value of its key instead of per node
   std::unordered_map<std::string, std::unordered_map<std::string, std::vector<int32_t>>> label_index;
   bool label_index_valid = false;       // Predicates() calls answered YKHOST_E_UNSUPPORTED (the Go side's fallback counter)
+  // ykhost_headroom_domains: label key → the group column of the node table — the bytewise-sorted distinct values of the key among this
+  // handle's nodes and, per node, the rank of its value (-1: the node does not carry the label) — valid while no node object changed
+  uint64_t node_objects_epoch = 0;
+  struct DomainColumn {
+    uint64_t epoch = 0;
+    std::vector<std::string> values;
+    std::vector<int32_t> group;
+  };
+  std::unordered_map<std::string, DomainColumn> domain_columns;  // (dropped as a whole when a node object changes)
+  uint64_t domain_columns_epoch = 0;
+  DomainColumn domain_united;  // node-sharded handle: the cluster-wide value list and this shard's column over it, of the last call
+  const std::vector<std::string>* domain_values_last = nullptr;  // the value list of the last ykhost_headroom_domains call
   int cfgR = 0, cfgKT = 0, cfgW = 0, cfgKD = -1, cfgKS = -1, cfgKP = -1;
 
   void clear_state() {
@@ -256,6 +268,9 @@ struct ykhost {
     uid_index = true;
     dirty_all = true;
     label_index_valid = false;
+    node_objects_epoch++;
+    domain_columns.clear();
+    domain_values_last = nullptr;
     dirty_nodes.clear();
     eval_dirty_nodes.clear();
     dirty_rows.clear();
@@ -1573,6 +1588,7 @@ static int apply_node(ykhost* h, const Node& n) {
   {
     int adopted = 0;
     h->label_index_valid = false;
+    h->node_objects_epoch++;
     auto it = h->node_ix.find(n.name);
     if (it == h->node_ix.end()) {
       h->node_store.emplace_back();
@@ -1608,6 +1624,7 @@ int32_t ykhost_remove_node(ykhost_t* h, const char* name) {
   auto it = h->node_ix.find(name);
   if (it == h->node_ix.end()) return 0;
   h->label_index_valid = false;
+  h->node_objects_epoch++;
   int idx = it->second;
   ensure_uid_index(h);
   int orphans = 0;
@@ -3419,6 +3436,180 @@ int32_t ykhost_headroom_by_key(ykhost_t* h, const char* allocation_key, int64_t*
   }
   const int32_t row = it->second->row;
   return ykhost_headroom(h, 1, &row, out16);
+}
+
+// ---- headroom per topology domain (ykpred_headroom_groups) --------------------------------------------------------------------------
+// The groups of a label key: ids are the ranks of the bytewise-sorted distinct values, a node without the label gets -1. The column is
+// kept per (key, node-table epoch). On a node-sharded handle the value lists of the shards are united first (lengths, then the lists
+// padded to the longest, as ykhost_comm_init unites the dictionaries): the ids are then cluster-wide, and the call is collective.
+namespace {
+int domain_column(ykhost* h, const std::string& key, int32_t world, const std::vector<std::string>** values, const std::vector<int32_t>** group) {
+  if (h->domain_columns_epoch != h->node_objects_epoch) {  // columns of another node table: none of them is asked for again
+    h->domain_columns.clear();
+    h->domain_columns_epoch = h->node_objects_epoch;
+  }
+  ykhost::DomainColumn& col = h->domain_columns[key];
+  const size_t N = h->nodes.size();
+  if (col.epoch != h->node_objects_epoch + 1 || col.group.size() != N) {
+    std::set<std::string> distinct;
+    for (size_t n = 0; n < N; ++n) {
+      auto it = h->nodes[n]->node.labels.find(key);
+      if (it != h->nodes[n]->node.labels.end()) distinct.insert(it->second);
+    }
+    col.values.assign(distinct.begin(), distinct.end());
+    col.group.assign(N, -1);
+    for (size_t n = 0; n < N; ++n) {
+      auto it = h->nodes[n]->node.labels.find(key);
+      if (it != h->nodes[n]->node.labels.end())
+        col.group[n] = (int32_t)(std::lower_bound(col.values.begin(), col.values.end(), it->second) - col.values.begin());
+    }
+    col.epoch = h->node_objects_epoch + 1;  // (0 = never built)
+  }
+  if (world <= 1) {
+    *values = &col.values;
+    *group = &col.group;
+    return 0;
+  }
+  std::string mine;
+  for (const std::string& v : col.values) mine += v + '\n';  // (a label value holds no line break)
+  std::vector<int64_t> lens((size_t)world);
+  const int64_t my_len = (int64_t)mine.size();
+  int rc = ykpred_comm_allgather_bytes(h->eng, &my_len, sizeof my_len, lens.data());
+  if (rc) return fail(h, std::string("ykpred_comm_allgather_bytes: ") + ykpred_last_error(h->eng), rc);
+  const int64_t longest = *std::max_element(lens.begin(), lens.end()) + 1;
+  mine.resize((size_t)longest, '\0');
+  std::string recv((size_t)(longest * world), '\0');
+  rc = ykpred_comm_allgather_bytes(h->eng, mine.data(), longest, &recv[0]);
+  if (rc) return fail(h, std::string("ykpred_comm_allgather_bytes: ") + ykpred_last_error(h->eng), rc);
+  std::set<std::string> all;
+  for (int g = 0; g < world; ++g) {
+    const std::string blob = recv.substr((size_t)(g * longest), (size_t)lens[(size_t)g]);
+    for (size_t at = 0; at < blob.size();) {
+      const size_t stop = blob.find('\n', at);
+      all.insert(blob.substr(at, stop - at));
+      at = stop + 1;
+    }
+  }
+  ykhost::DomainColumn& united = h->domain_united;
+  united.values.assign(all.begin(), all.end());
+  united.group.assign(N, -1);
+  for (size_t n = 0; n < N; ++n)
+    if (col.group[n] >= 0)
+      united.group[n] = (int32_t)(std::lower_bound(united.values.begin(), united.values.end(), col.values[(size_t)col.group[n]]) - united.values.begin());
+  *values = &united.values;
+  *group = &united.group;
+  return 0;
+}
+}  // namespace
+
+int32_t ykhost_headroom_domains(ykhost_t* h, int32_t n, const int32_t* pods, const int64_t* want, const char* label_key,
+                                int64_t* out_summary, int64_t* out_groups, int64_t groups_cap) {
+  YKHOST_LOCKED(h);
+  if (n < 0 || !label_key || (n > 0 && !out_summary)) return fail(h, "headroom_domains: bad argument", -1);
+  if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
+  int rc = sync(h);
+  if (rc) return rc;
+  int32_t world = 1;
+  ykpred_comm_info(h->eng, nullptr, &world, nullptr);
+  // (on a node-sharded handle the call is collective from here on: the indices and the wants are checked by the engine, whose agreement
+  // step makes every rank return the same error — a rank that returned here would leave the others waiting in the gather)
+  const int P = (int)h->pending.size();
+  if (world <= 1)
+    for (int i = 0; i < n; ++i) {
+      if ((pods ? pods[i] : i) < 0 || (pods ? pods[i] : i) >= P) return fail(h, "headroom_domains: ask index out of range", YKPRED_E_INVALID);
+      if (want && want[i] < 1) return fail(h, "headroom_domains: want must be at least 1", YKPRED_E_INVALID);
+    }
+  const std::vector<std::string>* values_p = nullptr;
+  const std::vector<int32_t>* group_p = nullptr;
+  rc = domain_column(h, label_key, world, &values_p, &group_p);
+  if (rc) return rc;
+  const std::vector<std::string>& values = *values_p;
+  const std::vector<int32_t>& group = *group_p;
+  h->domain_values_last = values_p;
+  const size_t G = values.size(), row = (G + 1) * YKPRED_GROUP_CELLS;
+  const size_t Ge = std::max<size_t>(G, 1), row_e = (Ge + 1) * YKPRED_GROUP_CELLS;  // (the engine wants a group: with no value, an empty one)
+  if (out_groups && groups_cap < (int64_t)((size_t)n * row))
+    return fail(h, "headroom_domains: out_groups holds fewer than n * (" + std::to_string(G) + " + 1) * 2 cells", YKPRED_E_INVALID);
+  // A routed ask gets status 1 without a device call; on a node-sharded handle every ask goes to the engine (ykhost_headroom).
+  std::vector<int32_t> list, slot;
+  std::vector<int64_t> wants;
+  for (int i = 0; i < n; ++i) {
+    const int r = pods ? pods[i] : i;
+    if (world <= 1 && h->enc.unsupported.count(h->pending[(size_t)r]->tpl)) {
+      int64_t* c = out_summary + (size_t)i * YKPRED_GROUP_SUMMARY;
+      std::fill(c, c + YKPRED_GROUP_SUMMARY, (int64_t)0);
+      c[0] = 1;
+      if (out_groups) std::fill(out_groups + (size_t)i * row, out_groups + (size_t)(i + 1) * row, (int64_t)0);
+    } else {
+      list.push_back(r);
+      slot.push_back(i);
+      wants.push_back(want ? want[i] : 1);
+    }
+  }
+  if (list.empty() && world <= 1) return (int32_t)G;
+  std::vector<int64_t> sums(list.size() * (size_t)YKPRED_GROUP_SUMMARY), rows(out_groups ? list.size() * row_e : 0);
+  rc = ykpred_headroom_groups(h->eng, (int32_t)list.size(), list.data(), wants.data(), (int32_t)Ge, group.data(), h->alloc_pre, h->alloc_filt,
+                              sums.data(), out_groups ? rows.data() : nullptr);
+  if (rc) return fail(h, std::string("ykpred_headroom_groups: ") + ykpred_last_error(h->eng), rc);
+  for (size_t k = 0; k < list.size(); ++k) {
+    memcpy(out_summary + (size_t)slot[k] * YKPRED_GROUP_SUMMARY, sums.data() + k * YKPRED_GROUP_SUMMARY, YKPRED_GROUP_SUMMARY * sizeof(int64_t));
+    if (out_groups) {
+      int64_t* dst = out_groups + (size_t)slot[k] * row;
+      memcpy(dst, rows.data() + k * row_e, G * YKPRED_GROUP_CELLS * sizeof(int64_t));
+      memcpy(dst + G * YKPRED_GROUP_CELLS, rows.data() + k * row_e + Ge * YKPRED_GROUP_CELLS, YKPRED_GROUP_CELLS * sizeof(int64_t));
+    }
+  }
+  return (int32_t)G;
+}
+
+int64_t ykhost_domain_values(ykhost_t* h, const char* label_key, char* out, int64_t len) {
+  YKHOST_LOCKED(h);
+  if (!label_key) return fail(h, "domain_values: bad argument", -1);
+  int32_t world = 1;
+  if (h->eng) ykpred_comm_info(h->eng, nullptr, &world, nullptr);
+  const std::vector<std::string>* values_p = nullptr;
+  const std::vector<int32_t>* group_p = nullptr;
+  const int rc = domain_column(h, label_key, world, &values_p, &group_p);
+  if (rc) return rc;
+  const std::vector<std::string>& values = *values_p;
+  std::string o = "[";
+  for (size_t i = 0; i < values.size(); ++i) {
+    if (i) o += ',';
+    js_str(o, values[i]);
+  }
+  o += ']';
+  copy_out(o, out, len);
+  return (int64_t)o.size() + 1;
+}
+
+// One ask named as the core names it, one label key, one crossing: the summary, and the two domains of it as label values.
+int32_t ykhost_headroom_domain_by_key(ykhost_t* h, const char* allocation_key, const char* label_key, int64_t want, int64_t* out_summary,
+                                      char* best, int64_t best_len, char* tightest, int64_t tightest_len) {
+  YKHOST_LOCKED(h);
+  if (!out_summary || !label_key) return fail(h, "headroom_domain_by_key: bad argument", -1);
+  std::fill(out_summary, out_summary + YKPRED_GROUP_SUMMARY, (int64_t)0);
+  copy_out("", best, best_len);
+  copy_out("", tightest, tightest_len);
+  ensure_uid_index(h);
+  auto it = h->by_uid.find(allocation_key ? allocation_key : "");
+  if (it == h->by_uid.end()) return YKHOST_E_POD_NOT_FOUND;
+  if (!it->second->ask) return fail(h, "pod holds no ask row", YKHOST_E_NOT_AN_ASK);
+  if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
+  int rc = sync(h);
+  if (rc) return rc;
+  auto un = h->enc.unsupported.find(it->second->tpl);
+  if (un != h->enc.unsupported.end()) {
+    out_summary[0] = 1;
+    return fail(h, "ask is not evaluated by the engine (route it to the CPU predicate manager): " + un->second, YKHOST_E_UNSUPPORTED);
+  }
+  const int32_t row = it->second->row;
+  rc = ykhost_headroom_domains(h, 1, &row, &want, label_key, out_summary, nullptr, 0);
+  if (rc < 0) return rc;
+  if (!h->domain_values_last) return 0;
+  const std::vector<std::string>& values = *h->domain_values_last;
+  if (out_summary[3] >= 0 && (size_t)out_summary[3] < values.size()) copy_out(values[(size_t)out_summary[3]], best, best_len);
+  if (out_summary[5] >= 0 && (size_t)out_summary[5] < values.size()) copy_out(values[(size_t)out_summary[5]], tightest, tightest_len);
+  return 0;
 }
 
 int32_t ykhost_pod_request_json(ykhost_t* h, int32_t pod, char* out, int32_t len) {

@@ -40,6 +40,10 @@ EXPLAIN_FIT, EXPLAIN_UNSUPPORTED, EXPLAIN_REASON0, EXPLAIN_RESOURCE0 = 9, 10, 12
 # nodes bound by [HEADROOM_BY_SLOTS] pod slots, [HEADROOM_BY_PORT] the host port, [HEADROOM_BY_RESOURCE0 + r] resource r
 HEADROOM_CELLS = 16
 HEADROOM_TOTAL, HEADROOM_NODES, HEADROOM_MAX, HEADROOM_STATUS, HEADROOM_BY_SLOTS, HEADROOM_BY_PORT, HEADROOM_BY_RESOURCE0 = 0, 1, 2, 3, 4, 5, 8
+# ykpred_headroom_groups: per (ask, group) int64[GROUP_CELLS] = copies, nodes (row G: the ungrouped nodes); per ask int64[GROUP_SUMMARY] =
+# status, groups with copies >= 1, groups with copies >= want, (most: group, copies), (tightest that holds want: group, copies), copies
+# on ungrouped nodes. Up to GROUP_LDS_MAX_GROUPS groups the kernel accumulates in LDS.
+GROUP_CELLS, GROUP_SUMMARY, GROUP_LDS_MAX_GROUPS = 2, 8, 63
 
 
 def plugin_mask(names):
@@ -706,6 +710,57 @@ class GpuPredicateManager:
             pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
             self._pcheck(self._P.ykpred_headroom_pod(self.engine, int(p), pre, filt, out.ctypes.data))
         return out[:self.num_nodes].copy()
+
+    def headroom_domains(self, pods=None, label_key=None, node_group=None, num_groups=None, want=None, groups=False, pre_mask=None,
+                         filt_mask=None):
+        """Headroom per topology domain (ykpred_headroom_groups): which zone, rack or host still takes `want` copies of an ask.
+        Either label_key (the groups are the bytewise-sorted values of that node label in the mirror, domain_values(label_key)
+        names them; allocation-phase lists) or an explicit node_group column (np.int32[N] of ids in [-1, num_groups), -1 = in no
+        group), which goes straight to the engine. pods: ask indices or UIDs, any order, repeats allowed; None = every ask. want: one
+        int or one per listed ask; None = 1. → np.int64[n, GROUP_SUMMARY], and with groups=True also np.int64[n, G + 1, GROUP_CELLS]
+        (row G: the nodes of no group)."""
+        if (label_key is None) == (node_group is None):
+            raise ValueError("headroom_domains takes either label_key or node_group")
+        if pods is None:
+            idx = np.arange(self.num_pods, dtype=np.int32)
+        else:
+            idx = np.ascontiguousarray([p if isinstance(p, (int, np.integer)) else self.pod_index(p) for p in pods], dtype=np.int32)
+        count = len(idx)
+        if want is None:
+            wants = None
+        else:
+            wants = np.ascontiguousarray(np.broadcast_to(np.asarray(want, dtype=np.int64), (count,)))
+        wptr = None if wants is None else wants.ctypes.data
+        summary = np.zeros((max(count, 1), GROUP_SUMMARY), dtype=np.int64)
+        if label_key is not None:
+            if pre_mask is not None or filt_mask is not None:
+                raise ValueError("explicit plugin masks go with an explicit node_group")
+            G = len(self.domain_values(label_key)) if groups else 0
+            rows = np.zeros((max(count, 1), G + 1, GROUP_CELLS), dtype=np.int64) if groups else None
+            rc = self._L.ykhost_headroom_domains(self._h, count, idx.ctypes.data, wptr, label_key.encode(), summary.ctypes.data,
+                                                 rows.ctypes.data if groups else None, rows.size if groups else 0)
+            if rc < 0:
+                self._check(rc)
+        else:
+            self.sync()
+            column = np.ascontiguousarray(node_group, dtype=np.int32)
+            if len(column) != self.num_nodes:
+                raise ValueError("node_group holds one id per node")
+            G = int(num_groups if num_groups is not None else (column.max() + 1 if len(column) else 1))
+            pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
+            rows = np.zeros((max(count, 1), max(G, 0) + 1, GROUP_CELLS), dtype=np.int64) if groups else None
+            self._pcheck(self._P.ykpred_headroom_groups(self.engine, count, idx.ctypes.data, wptr, G, column.ctypes.data, pre, filt,
+                                                        summary.ctypes.data, rows.ctypes.data if groups else None))
+        return (summary[:count].copy(), rows[:count].copy()) if groups else summary[:count].copy()
+
+    def domain_values(self, label_key):
+        """The values of a node label key in group-id order (bytewise sorted): what the ids of headroom_domains(label_key=...) name."""
+        need = self._L.ykhost_domain_values(self._h, label_key.encode(), None, 0)
+        if need < 0:
+            self._check(int(need))
+        buf = C.create_string_buffer(int(need))
+        self._L.ykhost_domain_values(self._h, label_key.encode(), buf, need)
+        return json.loads(buf.value.decode())
 
     def round_info(self):
         """ykpred_get_round_info: how the allocation rounds so far were decided (in batches / by the sequential kernel)."""
