@@ -38,7 +38,9 @@
 extern "C" {
 #endif
 
-/* (ykpred_headroom_groups + YKPRED_GROUP_CELLS / YKPRED_GROUP_SUMMARY arrived WITHIN version 4 too: dlsym("ykpred_headroom_groups"))
+/* (ykpred_headroom_spread + ykpred_headroom_spread_pod + YKPRED_SPREAD_HEADROOM_CELLS arrived WITHIN version 4 too:
+ *    dlsym("ykpred_headroom_spread"))
+ * (ykpred_headroom_groups + YKPRED_GROUP_CELLS / YKPRED_GROUP_SUMMARY arrived WITHIN version 4 too: dlsym("ykpred_headroom_groups"))
  * (ykpred_headroom + ykpred_headroom_pod + YKPRED_HEADROOM_CELLS arrived WITHIN version 4 as well, detected the same way:
  *    dlsym("ykpred_headroom"))
  * (ykpred_explain + YKPRED_EXPLAIN_BINS arrived WITHIN version 4, without a bump: a host that needs the call detects it by the
@@ -545,6 +547,56 @@ int32_t ykpred_headroom_groups(ykpred_engine_t* e, int32_t n_asks, const int32_t
                                const int32_t* node_group /* host, [N] */, uint32_t prefilter_plugins, uint32_t filter_plugins,
                                int64_t* out_summary /* host, [n_asks][YKPRED_GROUP_SUMMARY] */,
                                int64_t* out_groups /* host, [n_asks][num_groups + 1][YKPRED_GROUP_CELLS], may be NULL */);
+
+/* Headroom for asks with ONE hard spread constraint — the asks ykpred_headroom reports as coupled (status 2) because their verdicts read the
+ * topology histograms. With PodTopologySpread in the Filter list, the LIVE constraints of an ask's topology signature are those of kind
+ * SPREAD, and those of the InterPodAffinity kinds when InterPodAffinity is in both lists. The ask QUALIFIES when exactly one constraint c
+ * is live, it is of kind SPREAD, PodTopologySpread is in the PreFilter list too, and every node that takes a copy and carries c's key
+ * COUNTS for c (a node fails to count only when c honours a node-inclusion policy whose plugin is missing from the lists). Then, with
+ * cnt[d], present[d], minv = c's histogram row as ykpred_query prepares it:
+ *   cap(d)   = sum over the nodes n of domain d of replicas(a, n), replicas evaluated WITHOUT PodTopologySpread in the Filter list
+ *              (otherwise exactly ykpred_headroom's, the same device routine); nodes(d) = how many of them have replicas >= 1; a node
+ *              without the key takes no copy
+ *   self_match != 0:  M = min over present d of cnt[d] + cap(d); floor = 0 when fewer than min_domains domains are present, else M;
+ *                     copies(d) = clamp(floor + max_skew - cnt[d], 0, cap(d))
+ *   self_match == 0:  floor = minv; copies(d) = cap(d) if cnt[d] - minv <= max_skew, else 0
+ * which is what placing copies one after another until none fits leaves in each domain, in every placement order. All int64.
+ * out[i]:
+ *  [0]  sum of copies          [1]  domains with copies >= 1        [2]  most copies in one domain
+ *  [3]  status: 0 computed; 1 routed (YKPRED_SPEC_UNSUPPORTED); 2 still coupled (does not qualify): [0] = [2] = -1, the rest 0;
+ *       3 not coupled under these lists — ykpred_headroom answers — the rest 0
+ *  [4]  sum of cap             [5]  present domains                 [6]  floor
+ *  [7]  the lowest domain id with cnt + cap == M; -1 under the minDomains rule, with self_match == 0, or with no present domain
+ *  [8]  domains filled to capacity (copies == cap >= 1)   [9]  domains cut by the skew (0 < copies < cap)
+ *  [10] domains shut by it (cap >= 1, copies == 0)        [11] the domain with the most copies, lowest id on ties, -1 if none
+ *  [12] topology key index     [13] max_skew              [14] sum of nodes           [15] 0
+ * Status 0: [8] + [9] + [10] == domains with cap >= 1; [0] <= [4]; [4] <= cell [0] of ykpred_headroom called without PodTopologySpread
+ *   in the Filter list, equal when every fitting node carries the key.
+ * Everything else is ykpred_headroom's: distinct (spec, NodeName) tasks, any order, repeats allowed; reads the TABLES only, needs no
+ *   evaluation and invalidates none; prepares the topology histograms as ykpred_query does; counts as one query; roctx range
+ *   "ykpred:headroom_spread"; n_asks == 0 returns YKPRED_OK; N == 0 gives status and [12], [13] with [7] = [11] = -1. The same errors, plus
+ *   YKPRED_E_INVALID unless PodTopologySpread is in the Filter list. The per-task tables are ragged (a task owns the domains of its key) and
+ *   are worked through in chunks under ykpred_headroom_groups' budget (YKPRED_TUNE group_scratch_mb, group_chunk_tasks); a chunk whose
+ *   tasks all have at most YKPRED_GROUP_LDS_MAX_GROUPS domains accumulates in LDS, any other straight in the global table
+ *   (group_lds=0 forces the latter); integer adds, the same cells either way.
+ * NODE-SHARDED engines: COLLECTIVE. The agreement all-gather of ykpred_headroom also covers the chunking knobs; one all-reduce SUM (int64)
+ *   per chunk over table and flags; the copies are derived AFTER it from the (already cluster-wide) histograms: identical rows on every rank.
+ * ykpred_headroom_spread_pod: the rows behind ONE ask, out[d] = { cnt, cap, nodes, copies } for the *num_domains domains of its key.
+ *   YKPRED_E_UNSUPPORTED for an ask at a status other than 0; YKPRED_E_INVALID when max_domains < *num_domains (which is set). Collective on
+ *   a sharded engine like the first call. */
+#define YKPRED_SPREAD_HEADROOM_CELLS 16
+int32_t ykpred_headroom_spread(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks /* host, ask indices, any order, repeats allowed */,
+                               uint32_t prefilter_plugins, uint32_t filter_plugins, int64_t* out /* host, [n_asks][YKPRED_SPREAD_HEADROOM_CELLS] */);
+int32_t ykpred_headroom_spread_pod(ykpred_engine_t* e, int32_t pod_index, uint32_t prefilter_plugins, uint32_t filter_plugins, int32_t max_domains,
+                                   int64_t* out /* host, [max_domains][4]: cnt, cap, nodes, copies */, int32_t* num_domains);
+/* Where the one live spread constraint of an ask lives in the topology histograms: out = { status as cell [3] above (from the tables
+ * alone: a non-counting fitting node is not seen here), topology key index, first cell of the constraint's row in layout.spread_counts /
+ * spread_present, its number of cells (domains), max_skew, min_domains, self_match, flags (YKPRED_SPREAD_HONOR_*) }; at a status other
+ * than 0 the other cells are 0. What a host needs to read the row ykpred_headroom_spread fills from. Reads the tables only; valid until
+ * the spec or node tables change. YKPRED_E_INVALID for a bad pointer or index, or without PodTopologySpread in the Filter list. */
+#define YKPRED_SPREAD_CONSTRAINT_CELLS 8
+int32_t ykpred_headroom_spread_constraint(ykpred_engine_t* e, int32_t pod_index, uint32_t prefilter_plugins, uint32_t filter_plugins,
+                                          int32_t* out /* host, [YKPRED_SPREAD_CONSTRAINT_CELLS] */);
 
 /* PreemptionPredicates (predicate_manager.go:141-179): victims are described by their request vectors, in order. */
 int32_t ykpred_preemption(ykpred_engine_t* e, int32_t pod_index, int32_t node_index, int32_t num_victims,

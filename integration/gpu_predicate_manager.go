@@ -519,6 +519,41 @@ func (m *gpuPredicateManager) DomainHeadroom(pod *v1.Pod, labelKey string, want 
 	}
 }
 
+// SpreadHeadroom answers Headroom's question for a task group that carries ONE hard topologySpreadConstraint — the asks Headroom reports
+// as coupled (ok == false there): how many placeholders the cluster still takes while the constraint holds, in how many domains of the
+// constraint's key, and which domain takes the most. The engine sums Headroom's per-node copies per domain on the device and fills the
+// domains up to the skew bound (ykpred_headroom_spread); the result is what placing the copies one after another would leave, in any
+// order. ONE crossing: ykhost_headroom_spread_by_key looks the ask up by allocation key and hands the domain back as a label value.
+// ok == false when the pod is not a mirrored ask, is routed to the CPU predicate manager, the engine failed, or the ask does not qualify
+// (several live constraints, inter-pod affinity, or not coupled at all: Headroom answers then).
+func (m *gpuPredicateManager) SpreadHeadroom(pod *v1.Pod) (total, domains, most int64, mostDomain string, ok bool) {
+	if pod == nil {
+		return 0, 0, 0, "", false
+	}
+	var cells [16]C.int64_t
+	var best [256]C.char
+	uid := C.CString(string(pod.UID))
+	rc := C.ykhost_headroom_spread_by_key(m.host, uid, &cells[0], &best[0], 256)
+	C.free(unsafe.Pointer(uid))
+	switch {
+	case rc == 0 && cells[3] == 0:
+		return int64(cells[0]), int64(cells[1]), int64(cells[2]), C.GoString(&best[0]), true
+	case rc == 0:
+		return 0, 0, 0, "", false
+	case rc == C.YKHOST_E_UNSUPPORTED:
+		m.Counters.RoutedUnsupported.Add(1)
+		return 0, 0, 0, "", false
+	case rc == C.YKHOST_E_POD_NOT_FOUND || rc == C.YKHOST_E_NOT_AN_ASK:
+		m.Counters.RoutedNotMirrored.Add(1)
+		return 0, 0, 0, "", false
+	default:
+		m.Counters.RoutedOnError.Add(1)
+		log.Log(log.ShimPredicates).Warn("GPU predicate engine error, no spread headroom for the ask",
+			zap.String("error", C.GoString(C.ykhost_last_error(m.host))))
+		return 0, 0, 0, "", false
+	}
+}
+
 // ResidentStats: Predicates() calls answered from the mirrored resident answer, per pair because the node's column changed,
 // by whole-ask device queries, and the answer / failing-plugin fetches behind them.
 func (m *gpuPredicateManager) ResidentStats() (resident, dirtyColumn, query, answerFetches, codeFetches int64) {

@@ -277,6 +277,7 @@ struct ykpred_engine {
   DevBuf d_explain;  // ykpred_explain: task specs | task pins | [tasks][YKPRED_EXPLAIN_BINS] counts
   DevBuf d_headroom;  // ykpred_headroom: [tasks][YKPRED_HEADROOM_CELLS] cells | [tasks] max replicas | task specs | task pins
   DevBuf d_groups;  // ykpred_headroom_groups: summaries | pair wants | pair tasks | task specs | task pins | coupled | node groups | one table chunk
+  DevBuf d_spread_head;  // ykpred_headroom_spread: summaries | tasks | one table chunk (rows | non-counting flags | unsupported)
   DevBuf d_bytes_gather;  // ykpred_comm_allgather_bytes
   DevBuf d_topo_agree;  // node-sharded: the shape of every rank's topology histograms (agree_topology)
   u64 dict_digest = 0;  // ykpred_set_dictionary_digest
@@ -4863,6 +4864,226 @@ int32_t ykpred_headroom_groups(ykpred_engine_t* e, int32_t n_asks, const int32_t
     const int32_t pr = pair_index.at(std::make_pair(tasks.task_of[(size_t)i], want ? want[i] : (int64_t)1));
     memcpy(out_summary + (size_t)i * S, summaries.data() + (size_t)pr * S, S * sizeof(int64_t));
   }
+  return YKPRED_OK;
+}
+
+// Does a spec QUALIFY for ykpred_headroom_spread by its signature? → the status the host can decide (0 candidate, 2
+// still coupled, 3 not coupled under these lists) and, at 0, the signature and the position of its one live constraint in it.
+static int spread_live_constraint(const ykpred_engine* e, int32_t spec, uint32_t pre, uint32_t filt, int32_t* sig, int* at) {
+  *sig = -1, *at = -1;
+  if (!headroom_coupled(e, spec, pre, filt)) return 3;
+  if (!(pre & YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD)) return 2;  // (every Filter call is an error without the PreFilter state)
+  const bool ipa_live = (pre & YKPRED_PLUGIN_INTER_POD_AFFINITY) && (filt & YKPRED_PLUGIN_INTER_POD_AFFINITY);
+  const int32_t d = e->spec_sig_spread[(size_t)spec];
+  int live = 0, where = -1;
+  bool spread_only = true;
+  for (size_t j = 0; j < e->spread_sig[(size_t)d].size(); ++j) {
+    const bool is_spread = e->spread_sig[(size_t)d][j].kind == ykk::kKindSpread;
+    if (!is_spread && !ipa_live) continue;
+    ++live;
+    where = (int)j;
+    spread_only = spread_only && is_spread;
+  }
+  if (live != 1 || !spread_only) return 2;
+  *sig = d, *at = where;
+  return 0;
+}
+
+// Headroom of asks with ONE live hard spread constraint: k_headroom_spread gathers cap / nodes per domain of the
+// constraint's key, k_spread_fill derives the copies per domain and the summary from them and the resident histogram row. The table is
+// ragged — a task owns dom_size rows of its own key — and is worked through in TABLE CHUNKS under ykpred_headroom_groups' scratch budget
+// (group_scratch_mb, group_chunk_tasks); a chunk's accumulation form follows from its largest dom_size (group_lds). Both entry points run
+// this routine; `rows` (may be null) receives the [dom_size][4] rows of the FIRST task when that task came out at status 0.
+extern "C++" {
+static int32_t headroom_spread_run(ykpred_engine* e, const std::string& name, int32_t n_asks, const int32_t* asks, bool pointers_ok, uint32_t pre,
+                                   uint32_t filt, int64_t* out, std::vector<int64_t>* rows) {
+  static_assert(ykk::kSpreadHeadCells == YKPRED_SPREAD_HEADROOM_CELLS, "k_spread_fill writes the layout of ykpred.h");
+  constexpr size_t B = YKPRED_SPREAD_HEADROOM_CELLS, RC = ykk::kSpreadRowCells;
+  auto more_checks = [&](std::string* why) -> int {
+    if (!(filt & YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD)) return *why = name + ": PodTopologySpread must be in the Filter list (ykpred_headroom answers without it)", YKPRED_E_INVALID;
+    return YKPRED_OK;
+  };
+  u64 more = 0x9e3779b97f4a7c15ull;
+  more = (more ^ (u64)(uint32_t)e->group_scratch_mb) * 0x100000001b3ull;
+  more = (more ^ (u64)(uint32_t)e->group_chunk_tasks) * 0x100000001b3ull;
+  more = (more ^ (u64)(uint32_t)e->group_lds) * 0x100000001b3ull;
+  HeadroomTasks tasks;
+  bool run = false;
+  const int32_t rc = headroom_prepare(e, name, n_asks, asks, pointers_ok, pre, filt, more_checks, more, &tasks, &run);
+  if (!run) return rc;
+  const bool sharded = e->comm && e->comm_world > 1;
+  hipStream_t st = e->own_stream;
+  if (e->spread_dirty) TRY(build_spread_tables(e, st));
+  const size_t T = tasks.spec.size();
+  // Which tasks qualify, from the signature tables: exactly one LIVE constraint, of kind SPREAD, and the PreFilter of the plugin ran
+  // (without it every Filter call is an error and nothing is placed: the ask stays at status 2).
+  std::vector<int32_t> sig_row0(e->spread_sig.size() + 1, 0);
+  for (size_t d = 0; d < e->spread_sig.size(); ++d) sig_row0[d + 1] = sig_row0[d] + (int32_t)e->spread_sig[d].size();
+  std::vector<ykk::SpreadHeadTask> ht(T);
+  std::vector<int64_t> t_rows(T, 0);
+  for (size_t k = 0; k < T; ++k) {
+    ykk::SpreadHeadTask& h = ht[k];
+    h = ykk::SpreadHeadTask{tasks.spec[k], tasks.pin[k], -1, -1, 0, 2, 0};
+    int32_t d = -1;
+    int at = -1;
+    h.status = spread_live_constraint(e, tasks.spec[k], pre, filt, &d, &at);
+    if (h.status != 0) continue;
+    const ykpred_spread_t& c = e->spread_sig[(size_t)d][(size_t)at];
+    h.sig = d;
+    h.g = sig_row0[(size_t)d] + at;
+    h.status = 0;
+    t_rows[k] = (size_t)c.topology_key < e->h_domain_sizes.size() ? e->h_domain_sizes[(size_t)c.topology_key] : 0;
+  }
+  std::vector<int64_t> sums(T * B, 0);
+  if (e->N == 0 && !sharded) {
+    // (no node: no histogram was built and no kernel runs; the verdicts above are the whole answer. A shard without nodes of a sharded
+    // engine takes the other branch: it holds the cluster-wide histograms and joins the reduces)
+    for (size_t k = 0; k < T; ++k) {
+      int64_t* row = sums.data() + k * B;
+      const bool routed = (size_t)ht[k].spec < e->h_sflags.size() && (e->h_sflags[(size_t)ht[k].spec] & YKPRED_SPEC_UNSUPPORTED);
+      if (routed) ht[k].status = 1;  // (what k_spread_fill reads from the device's spec table)
+      row[3] = ht[k].status;
+      if (ht[k].status == 2) row[0] = row[2] = -1;
+      if (ht[k].status == 0) {
+        const ykpred_spread_t& c = e->spread_sig[(size_t)ht[k].sig][(size_t)(ht[k].g - sig_row0[(size_t)ht[k].sig])];
+        row[7] = row[11] = -1;
+        row[12] = c.topology_key;
+        row[13] = c.max_skew;
+      }
+    }
+    if (rows) rows->clear();
+  } else {
+    // Table chunks: consecutive tasks while their rows fit the budget (at least one task; group_chunk_tasks overrides the count).
+    const size_t budget = (size_t)e->group_scratch_mb << 20;
+    std::vector<size_t> chunk_begin{0};
+    size_t biggest = 0;
+    {
+      size_t bytes = 0, count = 0;
+      for (size_t k = 0; k < T; ++k) {
+        const size_t need = ((size_t)t_rows[k] * RC + 2) * sizeof(int64_t);
+        const bool full = e->group_chunk_tasks > 0 ? count >= (size_t)e->group_chunk_tasks : (count > 0 && bytes + need > budget);
+        if (full) {
+          chunk_begin.push_back(k);
+          bytes = 0, count = 0;
+        }
+        bytes += need;
+        ++count;
+        biggest = std::max(biggest, bytes);
+      }
+      chunk_begin.push_back(T);
+    }
+    auto up8 = [](size_t b) { return (b + 7) & ~(size_t)7; };
+    const size_t o_tasks = T * B * sizeof(int64_t), o_table = up8(o_tasks + T * sizeof(ykk::SpreadHeadTask));
+    HIPCHK(e->d_spread_head.ensure(o_table + biggest + 64));
+    char* base = e->d_spread_head.as<char>();
+    int64_t* d_summary = (int64_t*)base;
+    ykk::SpreadHeadTask* d_tasks = (ykk::SpreadHeadTask*)(base + o_tasks);
+    int64_t* d_table = (int64_t*)(base + o_table);
+    // (row0 counts from the start of the task's chunk)
+    for (size_t ci = 0; ci + 1 < chunk_begin.size(); ++ci) {
+      int64_t at = 0;
+      for (size_t k = chunk_begin[ci]; k < chunk_begin[ci + 1]; ++k) ht[k].row0 = at, at += t_rows[k];
+    }
+    HIPCHK(hipMemcpyAsync(d_tasks, ht.data(), T * sizeof(ykk::SpreadHeadTask), hipMemcpyHostToDevice, st));
+    const ykk::AffSigs as{e->d_sig_aff_flags.as<unsigned>(), e->d_sig_aff_off.as<int>(), e->d_sig_aff_terms.as<u64>(), e->d_sig_pre_off.as<int>(),
+                          e->d_sig_pre_terms.as<u64>()};
+    const uint32_t filt_fit = filt & ~(uint32_t)YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD;
+    for (size_t ci = 0; ci + 1 < chunk_begin.size(); ++ci) {
+      const size_t c0 = chunk_begin[ci], tc = chunk_begin[ci + 1] - c0;
+      size_t n_rows = 0;
+      int64_t widest = 0;
+      for (size_t k = c0; k < c0 + tc; ++k) n_rows += (size_t)t_rows[k], widest = std::max(widest, t_rows[k]);
+      int64_t* d_flags = d_table + n_rows * RC;
+      int64_t* d_unsupported = d_flags + tc;
+      const size_t cells = n_rows * RC + 2 * tc;
+      HIPCHK(hipMemsetAsync(d_table, 0, cells * sizeof(int64_t), st));
+      const dim3 grid((unsigned)((tc + ykk::kExplainTasks - 1) / ykk::kExplainTasks), (unsigned)(((size_t)e->N + ykk::kBlock - 1) / ykk::kBlock));
+      if (e->N == 0) {
+      } else if (widest <= ykk::kGroupLdsMaxGroups && e->group_lds != 0)
+        hipLaunchKernelGGL(ykk::k_headroom_spread<true>, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e), as, e->d_sig_tol.as<u64>(),
+                           (int)tc, d_tasks + c0, pre, filt_fit, (ykk::i64*)d_table, (ykk::i64*)d_flags, (ykk::i64*)d_unsupported);
+      else
+        hipLaunchKernelGGL(ykk::k_headroom_spread<false>, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e), as, e->d_sig_tol.as<u64>(),
+                           (int)tc, d_tasks + c0, pre, filt_fit, (ykk::i64*)d_table, (ykk::i64*)d_flags, (ykk::i64*)d_unsupported);
+      HIPCHK(hipGetLastError());
+      if (sharded) NCCLCHK(rccl()->AllReduce(d_table, d_table, cells, ncclInt64, ncclSum, e->comm, st));
+      hipLaunchKernelGGL(ykk::k_spread_fill, dim3((unsigned)((tc + ykk::kWavesPerBlock - 1) / ykk::kWavesPerBlock)), dim3(ykk::kBlock), 0, st, (int)tc,
+                         d_tasks + c0, spread_sigs(e), (ykk::i64*)d_table, (const ykk::i64*)d_flags, (const ykk::i64*)d_unsupported,
+                         (ykk::i64*)(d_summary + c0 * B));
+      HIPCHK(hipGetLastError());
+      if (rows && ci == 0) {
+        rows->assign((size_t)t_rows[0] * RC, 0);
+        if (!rows->empty()) HIPCHK(hipMemcpyAsync(rows->data(), d_table, rows->size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+      }
+      // (the next chunk reuses the table: the stream orders its fill behind this chunk's kernels and copy)
+    }
+    HIPCHK(hipMemcpyAsync(sums.data(), d_summary, T * B * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  for (int i = 0; i < n_asks; ++i) memcpy(out + (size_t)i * B, sums.data() + (size_t)tasks.task_of[(size_t)i] * B, B * sizeof(int64_t));
+  return YKPRED_OK;
+}
+}  // extern "C++"
+
+int32_t ykpred_headroom_spread(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, uint32_t pre, uint32_t filt, int64_t* out) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:headroom_spread");
+  if (e) e->n_queries++;
+  if (!e) return YKPRED_E_INVALID;
+  return headroom_spread_run(e, "headroom_spread", n_asks, asks, n_asks <= 0 || (asks && out), pre, filt, out, nullptr);
+}
+
+// The per-domain rows behind one ask's summary. On a sharded engine the whole computation is the collective one of ykpred_headroom_spread;
+// the argument checks that only this rank can fail come after it.
+int32_t ykpred_headroom_spread_pod(ykpred_engine_t* e, int32_t pod, uint32_t pre, uint32_t filt, int32_t max_domains, int64_t* out,
+                                   int32_t* num_domains) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:headroom_spread_pod");
+  if (e) e->n_queries++;
+  if (!e) return YKPRED_E_INVALID;
+  int64_t cells[YKPRED_SPREAD_HEADROOM_CELLS];
+  std::vector<int64_t> rows;
+  const int32_t rc = headroom_spread_run(e, "headroom_spread_pod", 1, &pod, num_domains != nullptr && max_domains >= 0 && (out || max_domains == 0), pre,
+                                         filt, cells, &rows);
+  if (rc != YKPRED_OK) return rc;
+  if (cells[3] != 0)
+    return fail(e, YKPRED_E_UNSUPPORTED, "headroom_spread_pod: the ask is at status " + std::to_string((long long)cells[3]) + " (ykpred_headroom_spread): it has no per-domain rows");
+  const size_t D = rows.size() / ykk::kSpreadRowCells;
+  *num_domains = (int32_t)D;
+  if ((size_t)max_domains < D) return fail(e, YKPRED_E_INVALID, "headroom_spread_pod: out holds fewer than " + std::to_string(D) + " domains");
+  if (D) memcpy(out, rows.data(), rows.size() * sizeof(int64_t));
+  return YKPRED_OK;
+}
+
+// Where the one live spread constraint of an ask lives in the topology histograms (layout.spread_counts / spread_present): what a host
+// needs to read the row ykpred_headroom_spread fills from. Tables only; no launch, nothing exchanged.
+int32_t ykpred_headroom_spread_constraint(ykpred_engine_t* e, int32_t pod, uint32_t pre, uint32_t filt, int32_t* out) {
+  YK_SERIALISE(e);
+  if (!e || !out) return fail(e, YKPRED_E_INVALID, "headroom_spread_constraint: bad argument");
+  if (!e->nodes_set || !e->specs_set || !e->pods_set) return fail(e, YKPRED_E_STATE, "headroom_spread_constraint: tables not uploaded");
+  if (pod < 0 || pod >= e->P) return fail(e, YKPRED_E_INVALID, "headroom_spread_constraint: index out of range");
+  if (!(filt & YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD)) return fail(e, YKPRED_E_INVALID, "headroom_spread_constraint: PodTopologySpread must be in the Filter list");
+  std::fill(out, out + YKPRED_SPREAD_CONSTRAINT_CELLS, (int32_t)0);
+  const int32_t spec = e->h_pod_spec[(size_t)pod];
+  int32_t d = -1;
+  int at = -1;
+  out[0] = spread_live_constraint(e, spec, pre, filt, &d, &at);
+  if ((size_t)spec < e->h_sflags.size() && (e->h_sflags[(size_t)spec] & YKPRED_SPEC_UNSUPPORTED)) out[0] = 1;
+  if (out[0] != 0) return YKPRED_OK;
+  int64_t off = 0;  // (the cell ranges build_spread_tables assigns: constraint after constraint, signature after signature)
+  for (int32_t dd = 0; dd <= d; ++dd)
+    for (size_t j = 0; j < e->spread_sig[(size_t)dd].size() && !(dd == d && (int)j == at); ++j) {
+      const int32_t kd = e->spread_sig[(size_t)dd][j].topology_key;
+      off += (size_t)kd < e->h_domain_sizes.size() ? e->h_domain_sizes[(size_t)kd] : 0;
+    }
+  const ykpred_spread_t& c = e->spread_sig[(size_t)d][(size_t)at];
+  out[1] = c.topology_key;
+  out[2] = (int32_t)off;
+  out[3] = (size_t)c.topology_key < e->h_domain_sizes.size() ? e->h_domain_sizes[(size_t)c.topology_key] : 0;
+  out[4] = c.max_skew;
+  out[5] = c.min_domains;
+  out[6] = c.self_match;
+  out[7] = (int32_t)c.flags;
   return YKPRED_OK;
 }
 

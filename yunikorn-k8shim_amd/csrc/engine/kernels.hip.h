@@ -3176,6 +3176,185 @@ __global__ __launch_bounds__(kBlock) void k_group_summary(int n_pairs, const int
   }
 }
 
+// ykpred_headroom_spread: headroom of an ask whose ONE live topology constraint is a hard PodTopologySpread constraint c (the host decides
+// that from the signature tables). Copies then interact only through c's histogram row, and the sequential loop over copies has a closed
+// result per DOMAIN of c's key. This kernel gathers its inputs: table[row0 + d] = { cnt, cap, nodes, copies } per domain
+// d, of which it adds cap = Σ replicas over the COUNTING nodes of the domain and nodes = how many of them take a copy; replicas is
+// ykpred_headroom's routine, called under the Filter mask WITHOUT the spread bit (the caller passes it so). A node without the label takes
+// no copy (the Filter fails it) and adds nothing. A node that takes a copy, carries the label and does NOT count for c (an inclusion
+// policy of c fails on it while the plugin lists do not filter it out) raises noncounting[task]: the loop's result then depends on the
+// node order, the task stays coupled. Grid and walk of k_headroom_groups: blockIdx.x = chunk of kExplainTasks tasks, blockIdx.y = 256
+// nodes, lane = node; node columns once per chunk, task data wave-uniform, a wave in which no lane fits skips the task. The lane's
+// domain id is the resident NodeTable.domain column (in NodeRegs). Two accumulation forms, as k_headroom_groups:
+//   use_lds  every task of the launch has dom_size <= kGroupLdsMaxGroups: the chunk's [kExplainTasks][kSpreadLdsRows][2] cells live in
+//            LDS, the block flushes its non-zero cells with one global integer add each;
+//   else     the adds go straight to the global table.
+// Integer adds only: the result does not depend on the order of arrival. A task with g < 0 does not qualify by its signature and is
+// skipped. unsupported[task] = 1 for a spec the engine does not evaluate (first node group alone).
+struct SpreadHeadTask {
+  int spec, pin;  // the task
+  int sig, g;     // its topology signature and the row of its one live constraint in SpreadSigs.c; g = -1: does not qualify
+  i64 row0;       // first row of the task in the chunk's table; it owns SpreadSigs.c[g].dom_size rows
+  int status;     // the host's verdict: 0 computed unless the kernels object, 2 still coupled, 3 not coupled under these lists
+  int pad;
+};
+constexpr int kSpreadHeadCells = 16;
+constexpr int kSpreadRowCells = 4;  // cnt, cap, nodes, copies
+constexpr int kSpreadLdsRows = kGroupLdsMaxGroups + 1;
+template <bool use_lds>
+__global__ __launch_bounds__(kBlock) void k_headroom_spread(NodeTable t, SpecTable s, AffSigs sig_aff, const u64* __restrict__ sig_tol, int n_tasks,
+                                                            const SpreadHeadTask* __restrict__ tasks, unsigned pre_mask, unsigned filt_mask,
+                                                            i64* __restrict__ table, i64* __restrict__ noncounting,
+                                                            i64* __restrict__ unsupported) {
+  __shared__ i64 sacc[use_lds ? kExplainTasks * kSpreadLdsRows * 2 : 1];
+  const int k0 = blockIdx.x * kExplainTasks, kend = min(k0 + kExplainTasks, n_tasks);
+  if (use_lds) {
+    for (int i = threadIdx.x; i < (kend - k0) * kSpreadLdsRows * 2; i += kBlock) sacc[i] = 0;
+    __syncthreads();
+  }
+  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+  int n = (blockIdx.y * kWavesPerBlock + wave) * kWave + lane;
+  const bool live = n < t.n;
+  if (!live) n = -1;
+  if (__ballot(live)) {  // (wave-uniform: a wave wholly past N skips the walk, not the barriers)
+    NodeRegs nr;
+    load_node(t, n, &nr);
+    const i64 slots = live ? (i64)t.allowed[n] - (i64)t.count[n] : 0;
+    for (int k = k0; k < kend; ++k) {
+      const SpreadHeadTask tk = tasks[k];
+      if (tk.g < 0) continue;  // (wave-uniform)
+      int binder = 0;
+      const int rep = live ? replicas(s, tk.spec, tk.pin, n, nr, slots, pre_mask, filt_mask, &binder) : 0;
+      if (!__ballot(rep > 0)) continue;  // (wave-uniform: no lane fits)
+      if (rep <= 0) continue;
+      const SpreadC c = s.spread.c[tk.g];
+      int dm = -1;
+#pragma unroll
+      for (int kd = 0; kd < kMaxKD; ++kd)
+        if (kd == c.kd) dm = nr.dom[kd];
+      if (dm < 0 || dm >= c.dom_size) continue;  // the label is missing: PodTopologySpread fails the node, it takes no copy
+      // A fitting lane has passed NodeAffinity's Filter (the DNF the Honor policy reads) when that plugin is in the Filter list, and
+      // TaintToleration's likewise: the inclusion policies are evaluated only for a policy whose plugin is missing (wave-uniform).
+      const bool ask_aff = (c.flags & kSpreadHonorAffinity) && !(filt_mask & kPlugAffinity);
+      const bool ask_tol = (c.flags & kSpreadHonorTaints) && !(filt_mask & kPlugTaint);
+      if ((ask_aff || ask_tol) && !spread_counts_here(c, spread_eligibility(t, s.spread, sig_aff, sig_tol, tk.sig, n))) {
+        atomicAdd((u64*)&noncounting[k], (u64)1);
+        continue;
+      }
+      if (use_lds) {
+        i64* cell = sacc + ((k - k0) * kSpreadLdsRows + dm) * 2;
+        atomicAdd((u64*)&cell[0], (u64)rep);
+        atomicAdd((u64*)&cell[1], (u64)1);
+      } else {
+        i64* cell = table + ((size_t)tk.row0 + dm) * kSpreadRowCells;
+        atomicAdd((u64*)&cell[1], (u64)rep);
+        atomicAdd((u64*)&cell[2], (u64)1);
+      }
+    }
+  }
+  if (use_lds) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < (kend - k0) * kSpreadLdsRows * 2; i += kBlock) {
+      const i64 v = sacc[i];  // (non-zero only in rows below the task's dom_size)
+      if (v) atomicAdd((u64*)&table[((size_t)tasks[k0 + i / (kSpreadLdsRows * 2)].row0 + (i / 2) % kSpreadLdsRows) * kSpreadRowCells + 1 + (i & 1)], (u64)v);
+    }
+  }
+  if (blockIdx.y == 0 && (int)threadIdx.x < kend - k0 && (s.flags[tasks[k0 + threadIdx.x].spec] & kSpecUnsupported)) unsupported[k0 + threadIdx.x] = 1;
+}
+
+// The fill of one task over its domain rows, one wave per task, after the table is complete (on a sharded engine: after the all-reduce;
+// the histograms are cluster-wide already, so every rank derives the same rows). With cnt / present / minv of the task's constraint c:
+//   self_match != 0:  M = min over present d of cnt[d] + cap[d]; floor = 0 when fewer than min_domains domains are present, else M;
+//                     copies(d) = clamp(floor + max_skew - cnt[d], 0, cap[d])
+//   self_match == 0:  copies do not move the histogram: floor = minv, copies(d) = cap[d] if cnt[d] - minv <= max_skew, else 0.
+// Lane l scans domains l, l + 64, ... ascending. Pass 1: the present domains and the minimum with the lowest id that attains it; pass 2:
+// cnt and copies into the row, and the summary (include/ykpred.h: YKPRED_SPREAD_HEADROOM_CELLS). Every butterfly comparison is total —
+// (value, id) — so the result is deterministic. Status: 1 for a task no shard evaluates, else the host's verdict, else 2 when a fitting
+// node does not count; a status other than 0 leaves [3] = status, for 2 also [0] = [2] = -1, and every other cell 0.
+__global__ __launch_bounds__(kBlock) void k_spread_fill(int n_tasks, const SpreadHeadTask* __restrict__ tasks, SpreadSigs sp, i64* __restrict__ table,
+                                                        const i64* __restrict__ noncounting, const i64* __restrict__ unsupported,
+                                                        i64* __restrict__ summary) {
+  const int lane = threadIdx.x % kWave, k = blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
+  if (k >= n_tasks) return;  // (wave-uniform, no barrier below)
+  const SpreadHeadTask tk = tasks[k];
+  i64* out = summary + (size_t)k * kSpreadHeadCells;
+  int status = unsupported[k] != 0 ? 1 : tk.status;
+  if (status == 0 && (tk.g < 0 || noncounting[k] != 0)) status = 2;
+  if (status != 0) {
+    if (lane < kSpreadHeadCells) out[lane] = lane == 3 ? status : (status == 2 && (lane == 0 || lane == 2)) ? -1 : 0;
+    return;
+  }
+  const SpreadC c = sp.c[tk.g];
+  i64* row = table + (size_t)tk.row0 * kSpreadRowCells;
+  const i64 kMost = 0x7fffffffffffffffll;
+  int nd = 0, mi = -1;
+  i64 mv = kMost;
+  for (int d = lane; d < c.dom_size; d += kWave)
+    if (sp.present[c.cnt_off + d]) {
+      ++nd;
+      const i64 v = (i64)sp.cnt[c.cnt_off + d] + row[d * kSpreadRowCells + 1];
+      if (v < mv) mv = v, mi = d;
+    }
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) {
+    nd += __shfl_xor(nd, off, kWave);
+    const i64 omv = (i64)__shfl_xor((long long)mv, off, kWave);
+    const int omi = __shfl_xor(mi, off, kWave);
+    if (omi >= 0 && (mi < 0 || omv < mv || (omv == mv && omi < mi))) mv = omv, mi = omi;
+  }
+  const bool self = c.self_match != 0, by_min = self && nd >= c.min_domains && mi >= 0;
+  const i64 low = self ? (by_min ? mv : 0) : (i64)sp.minv[tk.g];
+  i64 sum = 0, most = 0, caps = 0, nodes = 0;
+  int some = 0, best = -1, filled = 0, cut = 0, shut = 0;
+  for (int d = lane; d < c.dom_size; d += kWave) {
+    const i64 cnt = sp.cnt[c.cnt_off + d], cap = row[d * kSpreadRowCells + 1];
+    i64 cp;
+    if (self) cp = min(max(low + (i64)c.max_skew - cnt, (i64)0), cap);
+    else cp = cnt - low <= (i64)c.max_skew ? cap : 0;
+    row[d * kSpreadRowCells] = cnt;
+    row[d * kSpreadRowCells + 3] = cp;
+    sum += cp;
+    caps += cap;
+    nodes += row[d * kSpreadRowCells + 2];
+    some += cp >= 1;
+    if (cp > most) most = cp, best = d;
+    filled += cap >= 1 && cp == cap;
+    cut += cp > 0 && cp < cap;
+    shut += cap >= 1 && cp == 0;
+  }
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) {
+    sum += (i64)__shfl_xor((long long)sum, off, kWave);
+    caps += (i64)__shfl_xor((long long)caps, off, kWave);
+    nodes += (i64)__shfl_xor((long long)nodes, off, kWave);
+    some += __shfl_xor(some, off, kWave);
+    filled += __shfl_xor(filled, off, kWave);
+    cut += __shfl_xor(cut, off, kWave);
+    shut += __shfl_xor(shut, off, kWave);
+    const i64 omost = (i64)__shfl_xor((long long)most, off, kWave);
+    const int obest = __shfl_xor(best, off, kWave);
+    if (obest >= 0 && (best < 0 || omost > most || (omost == most && obest < best))) most = omost, best = obest;
+  }
+  if (lane == 0) {
+    out[0] = sum;
+    out[1] = some;
+    out[2] = best < 0 ? 0 : most;
+    out[3] = 0;
+    out[4] = caps;
+    out[5] = nd;
+    out[6] = low;
+    out[7] = by_min ? mi : -1;
+    out[8] = filled;
+    out[9] = cut;
+    out[10] = shut;
+    out[11] = best;
+    out[12] = c.kd;
+    out[13] = c.max_skew;
+    out[14] = nodes;
+    out[15] = 0;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // incremental column patch: only the bitmap columns of the listed (updated) nodes are re-evaluated
 // ---------------------------------------------------------------------------------------------------

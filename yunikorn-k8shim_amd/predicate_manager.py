@@ -44,6 +44,11 @@ HEADROOM_TOTAL, HEADROOM_NODES, HEADROOM_MAX, HEADROOM_STATUS, HEADROOM_BY_SLOTS
 # status, groups with copies >= 1, groups with copies >= want, (most: group, copies), (tightest that holds want: group, copies), copies
 # on ungrouped nodes. Up to GROUP_LDS_MAX_GROUPS groups the kernel accumulates in LDS.
 GROUP_CELLS, GROUP_SUMMARY, GROUP_LDS_MAX_GROUPS = 2, 8, 63
+# ykpred_headroom_spread: per ask int64[SPREAD_HEADROOM_CELLS] = copies, domains with a copy, most copies in a domain, status (0 computed,
+# 1 routed, 2 still coupled, 3 not coupled: headroom answers), sum of cap, present domains, floor, the domain that pins the floor, domains
+# filled / cut / shut, the domain with the most copies, topology key index, maxSkew, fitting nodes, 0; per (ask, domain)
+# int64[SPREAD_ROW_CELLS] = cnt, cap, nodes, copies
+SPREAD_HEADROOM_CELLS, SPREAD_ROW_CELLS = 16, 4
 
 
 def plugin_mask(names):
@@ -761,6 +766,70 @@ class GpuPredicateManager:
         buf = C.create_string_buffer(int(need))
         self._L.ykhost_domain_values(self._h, label_key.encode(), buf, need)
         return json.loads(buf.value.decode())
+
+    def headroom_spread(self, pods=None, pre_mask=None, filt_mask=None):
+        """Headroom of asks with ONE hard topology spread constraint (ykpred_headroom_spread) — those headroom() reports as coupled:
+        np.int64[n, SPREAD_HEADROOM_CELLS]. pods: ask indices or UIDs in any order, repeats allowed; None = every ask. Allocation-phase
+        lists; explicit masks go to the engine directly, like headroom. Needs no evaluation and disturbs none. [3] is the status: 0
+        computed, 1 routed, 2 still coupled (total = max = -1), 3 not coupled under these lists (headroom() answers)."""
+        if pods is None:
+            count, ptr = self.num_pods, None
+        else:
+            idx = [p if isinstance(p, (int, np.integer)) else self.pod_index(p) for p in pods]
+            arr = np.ascontiguousarray(idx, dtype=np.int32)
+            count, ptr = len(arr), arr.ctypes.data
+        out = np.zeros((max(count, 1), SPREAD_HEADROOM_CELLS), dtype=np.int64)
+        if pre_mask is None and filt_mask is None:
+            self._check(self._L.ykhost_headroom_spread(self._h, count, ptr, out.ctypes.data))
+        else:
+            self.sync()
+            pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
+            if ptr is None:
+                arr = np.arange(count, dtype=np.int32)
+                ptr = arr.ctypes.data
+            self._pcheck(self._P.ykpred_headroom_spread(self.engine, count, ptr, pre, filt, out.ctypes.data))
+        return out[:count].copy()
+
+    def headroom_spread_domains(self, pod, pre_mask=None, filt_mask=None):
+        """The per-domain rows behind headroom_spread for ONE ask (index or UID): (cells np.int64[SPREAD_HEADROOM_CELLS], rows
+        np.int64[D, SPREAD_ROW_CELLS] = cnt, cap, nodes, copies per domain of the constraint's key, values) — values are the domains'
+        label values in id order (None with explicit masks, which go to the engine directly: one run for the cells, one for the rows,
+        the table sized by headroom_spread_constraint). At a status other than 0 the rows are empty."""
+        p = int(pod if isinstance(pod, (int, np.integer)) else self.pod_index(pod))
+        cells = np.zeros(SPREAD_HEADROOM_CELLS, dtype=np.int64)
+        if pre_mask is None and filt_mask is None:
+            cap, vlen = 64, 4096
+            while True:
+                rows = np.zeros((cap, SPREAD_ROW_CELLS), dtype=np.int64)
+                buf = C.create_string_buffer(vlen)
+                rc = self._check(self._L.ykhost_headroom_spread_domains(self._h, p, cells.ctypes.data, rows.ctypes.data, cap, buf, vlen))
+                if rc > cap:  # (fewer rows than domains: the size needed came back)
+                    cap = rc
+                elif rc > 0 and not buf.value.endswith(b"]"):  # (the value list was cut)
+                    vlen *= 16
+                else:
+                    return cells, rows[:rc].copy(), json.loads(buf.value.decode())
+        where = self.headroom_spread_constraint(p, pre_mask=pre_mask, filt_mask=filt_mask)  # (the row's size: no launch)
+        pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
+        one = np.array([p], dtype=np.int32)
+        self._pcheck(self._P.ykpred_headroom_spread(self.engine, 1, one.ctypes.data, pre, filt, cells.ctypes.data))
+        if cells[3] != 0:
+            return cells, np.zeros((0, SPREAD_ROW_CELLS), dtype=np.int64), None
+        count = C.c_int32(0)
+        rows = np.zeros((max(int(where[3]), 1), SPREAD_ROW_CELLS), dtype=np.int64)
+        self._pcheck(self._P.ykpred_headroom_spread_pod(self.engine, p, pre, filt, len(rows), rows.ctypes.data, C.byref(count)))
+        return cells, rows[:count.value].copy(), None
+
+    def headroom_spread_constraint(self, pod, pre_mask=None, filt_mask=None):
+        """Where the one live spread constraint of an ask (index or UID) lies in the topology histograms
+        (ykpred_headroom_spread_constraint): np.int32[8] = status from the tables alone, topology key index, first cell and number of
+        cells of its row in layout().spread_counts / spread_present, maxSkew, minDomains, self-match, flags. No device work."""
+        p = int(pod if isinstance(pod, (int, np.integer)) else self.pod_index(pod))
+        self.sync()
+        pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
+        out = np.zeros(8, dtype=np.int32)
+        self._pcheck(self._P.ykpred_headroom_spread_constraint(self.engine, p, pre, filt, out.ctypes.data))
+        return out
 
     def round_info(self):
         """ykpred_get_round_info: how the allocation rounds so far were decided (in batches / by the sequential kernel)."""
