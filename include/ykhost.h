@@ -302,6 +302,25 @@ int32_t ykhost_headroom_spread_domains(ykhost_t* h, int32_t pod, int64_t* out_su
                                        int32_t max_domains, char* values, int64_t values_len);
 int32_t ykhost_headroom_spread_by_key(ykhost_t* h, const char* allocation_key, int64_t* out16 /* [16] */, char* best, int64_t best_len);
 
+/* Headroom of asks with required pod (anti-)affinity (ykpred.h: ykpred_headroom_affinity) — the other fallback when ykhost_headroom
+ * reports an ask as coupled (status 2): how many placeholders of a task group with "one executor per host" (or any required
+ * podAffinity / podAntiAffinity whose copies meet on one topology key) the cluster still takes, and in which domains. Always the
+ * ALLOCATION-phase plugin lists. Each call syncs and uploads the spec effects when the spec table moved since the last upload.
+ *   ykhost_headroom_affinity          ONE engine call for the listed asks (NULL = asks 0..n-1): out_cells[i] = the
+ *                                     YKPRED_AFFINITY_HEADROOM_CELLS cells. A routed ask gets status 1 without a device call. → 0 or an
+ *                                     error. Collective on a node-sharded handle: every rank passes the same asks.
+ *   ykhost_headroom_affinity_domains  one ask at status 0 or 4: the cells, its rows out_rows[d] = { cnt, cap, nodes, copies } per domain
+ *                                     with the OUTSIDE row (nodes without the key) at out_rows[D], and the domains' label VALUES in id
+ *                                     order as a JSON array → D, or an error < 0; 0 and "[]" at any other status. out_rows holds
+ *                                     max_domains + 1 rows; with max_domains < D nothing but the cells is written: call again with room.
+ *   ykhost_headroom_affinity_by_key   ONE crossing for one ask by allocation key (pod UID): the cells, and the domain with the most
+ *                                     copies as a label VALUE ("" when there is none). → 0, or the errors of ykhost_headroom_by_key
+ *                                     (YKHOST_E_UNSUPPORTED with out16[3] = 1). */
+int32_t ykhost_headroom_affinity(ykhost_t* h, int32_t n, const int32_t* asks /* NULL = asks 0..n-1 */, int64_t* out_cells /* [n][16] */);
+int32_t ykhost_headroom_affinity_domains(ykhost_t* h, int32_t pod, int64_t* out_summary /* [16] */, int64_t* out_rows /* [max_domains + 1][4] */,
+                                         int32_t max_domains, char* values, int64_t values_len);
+int32_t ykhost_headroom_affinity_by_key(ykhost_t* h, const char* allocation_key, int64_t* out16 /* [16] */, char* best, int64_t best_len);
+
 /* Engine calls that came back YKPRED_E_DEVICE / YKPRED_E_NOMEM so far (failed allocation, lost device). Each one marks the whole
  * device state stale: the failing call returns its error (Predicates() < 0: the Go manager routes the ask to the CPU predicate
  * manager — SURVEY.md §5, "must degrade, never fail scheduling"), the mirror stays intact, and the next ykhost_sync /

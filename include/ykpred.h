@@ -38,7 +38,9 @@
 extern "C" {
 #endif
 
-/* (ykpred_headroom_spread + ykpred_headroom_spread_pod + YKPRED_SPREAD_HEADROOM_CELLS arrived WITHIN version 4 too:
+/* (ykpred_headroom_affinity + ykpred_headroom_affinity_pod + YKPRED_AFFINITY_HEADROOM_CELLS arrived WITHIN version 4 too:
+ *    dlsym("ykpred_headroom_affinity"))
+ * (ykpred_headroom_spread + ykpred_headroom_spread_pod + YKPRED_SPREAD_HEADROOM_CELLS arrived WITHIN version 4 too:
  *    dlsym("ykpred_headroom_spread"))
  * (ykpred_headroom_groups + YKPRED_GROUP_CELLS / YKPRED_GROUP_SUMMARY arrived WITHIN version 4 too: dlsym("ykpred_headroom_groups"))
  * (ykpred_headroom + ykpred_headroom_pod + YKPRED_HEADROOM_CELLS arrived WITHIN version 4 as well, detected the same way:
@@ -597,6 +599,63 @@ int32_t ykpred_headroom_spread_pod(ykpred_engine_t* e, int32_t pod_index, uint32
 #define YKPRED_SPREAD_CONSTRAINT_CELLS 8
 int32_t ykpred_headroom_spread_constraint(ykpred_engine_t* e, int32_t pod_index, uint32_t prefilter_plugins, uint32_t filter_plugins,
                                           int32_t* out /* host, [YKPRED_SPREAD_CONSTRAINT_CELLS] */);
+
+/* Headroom for asks with required pod (anti-)affinity — the other asks ykpred_headroom reports as coupled (status 2): "one executor per
+ * host" and its kin. InterPodAffinity must be in both lists; the LIVE constraints of an ask's topology signature are then those of kind
+ * POD_AFFINITY, POD_ANTI_AFFINITY and EXISTING_ANTI_AFFINITY, and those of kind SPREAD when PodTopologySpread is in the Filter list.
+ * With w(g) = what one assumed pod of the ask's spec adds to the selector class of constraint g (ykpred_set_spec_effects; 0 for
+ * selector_class == -1), the ask QUALIFIES when no SPREAD constraint is live, at least one constraint of the other kinds is, and the
+ * SELF-CONTRIBUTING anti rows (kind POD_ANTI_AFFINITY or EXISTING_ANTI_AFFINITY, w > 0) all lie on ONE topology key k*. Per domain d of
+ * the task's key:
+ *   cap(d)   = sum over the nodes n of d of replicas(a, n) — ykpred_headroom's routine under these lists, InterPodAffinity included: the
+ *              static verdict of ykpred_query against the current histograms; nodes(d) = how many of them take a copy;
+ *   cnt(d)   = sum over the live anti rows on that key of their histogram cell.
+ * Nodes WITHOUT the key go to an OUTSIDE row (an anti-affinity row passes them, and a copy placed there moves no cell).
+ *   mode 0, static: no self-contributing anti row; key = that of the first live row; copies(d) = cap(d).
+ *   mode 1, one per domain: key = k*; copies(d) = min(cap(d), 1); the outside row keeps its cap. The first copy placed in d shuts d,
+ *     no placement opens a domain: every open domain ends with exactly one copy, in every placement order.
+ *   mode 2, bootstrap: a POD_AFFINITY row with self_match != 0 and w > 0 while no pod matches anywhere (the sum of minv over the
+ *     affinity rows is 0). The first copy lands anywhere and pins its domain: the result depends on the order. With exactly ONE affinity
+ *     row and no self-contributing anti row: status 4, copies(d) = cap(d) = what the gang gets if it starts in d. Otherwise status 2.
+ * out[i]:
+ *  [0]  sum of copies, the outside row included    [1]  domains with copies >= 1        [2]  most copies in one domain
+ *  [3]  status: 0 computed; 1 routed (YKPRED_SPEC_UNSUPPORTED): every other cell 0; 2 still coupled (a live SPREAD constraint beside the
+ *       affinity ones, self-contributing anti rows on two keys, a bootstrap that does not qualify): [0] = [2] = -1, the rest 0;
+ *       3 no InterPodAffinity constraint is live — ykpred_headroom or ykpred_headroom_spread answers — the rest 0;
+ *       4 bootstrap: [0] = -1, [2] and [11] = the best starting domain, every other cell as computed
+ *  [4]  sum of cap over the domains                [5]  domains with cnt > 0 (blocked)   [6]  copies outside
+ *  [7]  nodes outside that take a copy             [8]  domains filled (copies == cap >= 1)
+ *  [9]  domains cut (0 < copies < cap)             [10] 0
+ *  [11] the domain with the most copies, lowest id on ties, -1 if none                   [12] topology key index
+ *  [13] mode                                       [14] sum of nodes, outside included   [15] 0
+ * Status 0: [8] + [9] == domains with cap >= 1; [0] <= [4] + [6]; in mode 1 [0] == [1] + [6].
+ * Everything else is ykpred_headroom_spread's: tasks, tables only, one query, chunks under group_scratch_mb / group_chunk_tasks, LDS
+ *   accumulation while every task of a chunk has at most YKPRED_GROUP_LDS_MAX_GROUPS domains (group_lds=0 forces the global table),
+ *   integer adds; roctx range "ykpred:headroom_affinity"; N == 0 gives status, [12], [13] with [11] = -1. The same errors, with
+ *   YKPRED_E_INVALID unless InterPodAffinity AND NodeResourcesFit are in both lists, and YKPRED_E_UNSUPPORTED when the spec effects are
+ *   not uploaded for the current spec table (the rule of ykpred_allocate_round).
+ * NODE-SHARDED engines: COLLECTIVE. The agreement all-gather covers both of those verdicts, the knobs and the effects version: no rank
+ *   exits alone. One all-reduce SUM (int64) per chunk over table and flags; bootstrap and the copies are derived AFTER it from the
+ *   (already cluster-wide) histograms: identical rows on every rank.
+ * ykpred_headroom_affinity_pod: the rows behind ONE ask, out[d] = { cnt, cap, nodes, copies } for the *num_domains domains of its key,
+ *   out[*num_domains] = the outside row. Status 0 and 4 only, else YKPRED_E_UNSUPPORTED; YKPRED_E_INVALID when max_domains <
+ *   *num_domains (which is set). Collective on a sharded engine like the first call. */
+#define YKPRED_AFFINITY_HEADROOM_CELLS 16
+int32_t ykpred_headroom_affinity(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks /* host, ask indices, any order, repeats allowed */,
+                                 uint32_t prefilter_plugins, uint32_t filter_plugins, int64_t* out /* host, [n_asks][YKPRED_AFFINITY_HEADROOM_CELLS] */);
+int32_t ykpred_headroom_affinity_pod(ykpred_engine_t* e, int32_t pod_index, uint32_t prefilter_plugins, uint32_t filter_plugins, int32_t max_domains,
+                                     int64_t* out /* host, [max_domains + 1][4]: cnt, cap, nodes, copies */, int32_t* num_domains);
+
+/* Where the cells behind cnt lie in the topology histograms: out = { status as cell [3] above from the tables and effects alone (bootstrap
+ * is not seen here: 0 where the call may say 4 or, for a bootstrap that does not qualify, 2), topology key index, mode (0 / 1), number
+ * of domains, number of live anti rows on the key, then the first cell in layout.spread_counts of each of them (the first
+ * YKPRED_AFFINITY_CONSTRAINT_ROWS; each row has as many cells as the key has domains) }; at a status other than 0 the other cells are 0.
+ * Reads the tables only; valid until the spec or node tables change. YKPRED_E_INVALID for a bad pointer or index, or without
+ * InterPodAffinity in both lists; YKPRED_E_UNSUPPORTED without current spec effects. */
+#define YKPRED_AFFINITY_CONSTRAINT_ROWS 11
+#define YKPRED_AFFINITY_CONSTRAINT_CELLS 16
+int32_t ykpred_headroom_affinity_constraint(ykpred_engine_t* e, int32_t pod_index, uint32_t prefilter_plugins, uint32_t filter_plugins,
+                                            int32_t* out /* host, [YKPRED_AFFINITY_CONSTRAINT_CELLS] */);
 
 /* PreemptionPredicates (predicate_manager.go:141-179): victims are described by their request vectors, in order. */
 int32_t ykpred_preemption(ykpred_engine_t* e, int32_t pod_index, int32_t node_index, int32_t num_victims,

@@ -554,6 +554,44 @@ func (m *gpuPredicateManager) SpreadHeadroom(pod *v1.Pod) (total, domains, most 
 	}
 }
 
+// AffinityHeadroom answers Headroom's question for a task group with required pod (anti-)affinity — "one executor per host" and its
+// kin, which Headroom reports as coupled (ok == false there): how many placeholders the cluster still takes, in how many domains of the
+// key its copies meet on, and which domain takes the most. The engine sums Headroom's per-node copies — under the static inter-pod
+// affinity verdict — per domain on the device and keeps one copy per domain where a copy shuts its domain for the next
+// (ykpred_headroom_affinity); the result is what placing the copies one after another would leave, in any order. ONE crossing:
+// ykhost_headroom_affinity_by_key looks the ask up by allocation key and hands the domain back as a label value. bootstrap == true
+// (status 4): the group's required affinity matches nobody but its own members, so the first member may start anywhere and pins the
+// domain; total is then unknown (-1) and most / mostDomain name the best domain to start in. ok == false when the pod is not a mirrored
+// ask, is routed to the CPU predicate manager, the engine failed, or the ask does not qualify (a hard spread constraint beside the
+// terms, self anti-affinity on two keys, or no inter-pod affinity at all: Headroom or SpreadHeadroom answers then).
+func (m *gpuPredicateManager) AffinityHeadroom(pod *v1.Pod) (total, domains, most int64, mostDomain string, bootstrap, ok bool) {
+	if pod == nil {
+		return 0, 0, 0, "", false, false
+	}
+	var cells [16]C.int64_t
+	var best [256]C.char
+	uid := C.CString(string(pod.UID))
+	rc := C.ykhost_headroom_affinity_by_key(m.host, uid, &cells[0], &best[0], 256)
+	C.free(unsafe.Pointer(uid))
+	switch {
+	case rc == 0 && (cells[3] == 0 || cells[3] == 4):
+		return int64(cells[0]), int64(cells[1]), int64(cells[2]), C.GoString(&best[0]), cells[3] == 4, true
+	case rc == 0:
+		return 0, 0, 0, "", false, false
+	case rc == C.YKHOST_E_UNSUPPORTED:
+		m.Counters.RoutedUnsupported.Add(1)
+		return 0, 0, 0, "", false, false
+	case rc == C.YKHOST_E_POD_NOT_FOUND || rc == C.YKHOST_E_NOT_AN_ASK:
+		m.Counters.RoutedNotMirrored.Add(1)
+		return 0, 0, 0, "", false, false
+	default:
+		m.Counters.RoutedOnError.Add(1)
+		log.Log(log.ShimPredicates).Warn("GPU predicate engine error, no affinity headroom for the ask",
+			zap.String("error", C.GoString(C.ykhost_last_error(m.host))))
+		return 0, 0, 0, "", false, false
+	}
+}
+
 // ResidentStats: Predicates() calls answered from the mirrored resident answer, per pair because the node's column changed,
 // by whole-ask device queries, and the answer / failing-plugin fetches behind them.
 func (m *gpuPredicateManager) ResidentStats() (resident, dirtyColumn, query, answerFetches, codeFetches int64) {

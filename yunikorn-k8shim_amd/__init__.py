@@ -8,6 +8,7 @@ from . import build  # noqa: F401
 from .predicate_manager import (ALL_PLUGINS, EXPLAIN_BINS, EXPLAIN_FIT, EXPLAIN_REASON0, EXPLAIN_RESOURCE0,  # noqa: F401
                                 EXPLAIN_UNSUPPORTED, GROUP_CELLS, GROUP_LDS_MAX_GROUPS, GROUP_SUMMARY, HEADROOM_BY_PORT, HEADROOM_BY_RESOURCE0, HEADROOM_BY_SLOTS, HEADROOM_CELLS,
                                 HEADROOM_MAX, HEADROOM_NODES, HEADROOM_STATUS, HEADROOM_TOTAL, PLUGIN_BITS, SPREAD_HEADROOM_CELLS, SPREAD_ROW_CELLS,
+                                AFFINITY_HEADROOM_CELLS,
                                 GpuPredicateManager,
                                 PredicateError, UnsupportedAsk, plugin_mask)
 

@@ -278,6 +278,7 @@ struct ykpred_engine {
   DevBuf d_headroom;  // ykpred_headroom: [tasks][YKPRED_HEADROOM_CELLS] cells | [tasks] max replicas | task specs | task pins
   DevBuf d_groups;  // ykpred_headroom_groups: summaries | pair wants | pair tasks | task specs | task pins | coupled | node groups | one table chunk
   DevBuf d_spread_head;  // ykpred_headroom_spread: summaries | tasks | one table chunk (rows | non-counting flags | unsupported)
+  DevBuf d_aff_head;  // ykpred_headroom_affinity: summaries | tasks | one table chunk (rows | unsupported)
   DevBuf d_bytes_gather;  // ykpred_comm_allgather_bytes
   DevBuf d_topo_agree;  // node-sharded: the shape of every rank's topology histograms (agree_topology)
   u64 dict_digest = 0;  // ykpred_set_dictionary_digest
@@ -350,6 +351,7 @@ struct ykpred_engine {
   int early_counts = 1;             // early_counts: 0 = class counts by the writers and the per-ask scatter behind them (the round-4 order)
   int group_lds = -1;               // group_lds: k_headroom_groups accumulates in LDS (1, wherever the chunk's table fits kGroupLdsBytes) or straight in the global table (0); -1 = LDS wherever it fits
   int group_scratch_mb = 256;       // group_scratch_mb: the budget of one table chunk of ykpred_headroom_groups (0 = one task per chunk)
+  int affinity_fill_waves = 0;      // affinity_fill_waves: waves per task of k_affinity_fill (1 or 4); 0 = the workgroup from kAffFillWideFrom domains on
   int group_chunk_tasks = 0;        // group_chunk_tasks: tasks per table chunk whatever the budget says (0 = from the budget): several chunks on a small table
   int max_lds_bytes = 64 * 1024;   // opt-in dynamic LDS limit of the device (hipDeviceAttributeMaxSharedMemoryPerBlock)
   int num_cus = 256;               // compute units of the device (hipDeviceAttributeMultiprocessorCount)
@@ -377,6 +379,7 @@ struct ykpred_engine {
   bool fx_contrib = false, fx_ports = false;  // some spec adds to a count column / occupies a dictionary host port
   std::vector<int32_t> h_fx_off;              // [S + 1] the contribution rows' offsets, host copy
   std::vector<int32_t> h_fx_cls;              // the selector class of every contribution row, host copy
+  std::vector<int32_t> h_fx_cnt;              // ... and what it adds to the class (ykpred_headroom_affinity: w per constraint row)
   std::vector<uint8_t> h_fx_occupies;         // [S] the spec's pods occupy a host port once on a node
   DevBuf d_patches, d_rows, d_row_count, d_row_best;
   unsigned last_pre = 0, last_filt = 0;  // plugin lists of the last full evaluation (ykpred_eval_nodes must match them)
@@ -1715,6 +1718,7 @@ int32_t ykpred_create(const ykpred_config_t* cfg, ykpred_engine_t** out) {
       else if (key == "group_lds") e->group_lds = val;
       else if (key == "group_scratch_mb") e->group_scratch_mb = std::max(val, 0);
       else if (key == "group_chunk_tasks") e->group_chunk_tasks = std::max(val, 0);
+      else if (key == "affinity_fill_waves") e->affinity_fill_waves = val;
       else {
         g_create_error = "YKPRED_TUNE: unknown key '" + key + "'";
         delete e;
@@ -3394,6 +3398,7 @@ int32_t ykpred_set_spec_effects(ykpred_engine_t* e, const ykpred_spec_effects_t*
   e->fx_ports = false;
   e->h_fx_off.clear();
   e->h_fx_cls.clear();
+  e->h_fx_cnt.clear();
   if (fx->contrib_off) {
     const int total = fx->contrib_off[S];
     if (fx->contrib_off[0] != 0 || total < 0 || (total > 0 && (!fx->contrib_class || !fx->contrib_count)))
@@ -3406,6 +3411,7 @@ int32_t ykpred_set_spec_effects(ykpred_engine_t* e, const ykpred_spec_effects_t*
     TRY(upload(e, e->d_fx_off, fx->contrib_off, S + 1, st));
     e->h_fx_off.assign(fx->contrib_off, fx->contrib_off + S + 1);  // (a batched round's prefix rule asks which specs move which histograms)
     if (total > 0) e->h_fx_cls.assign(fx->contrib_class, fx->contrib_class + total);
+    if (total > 0) e->h_fx_cnt.assign(fx->contrib_count, fx->contrib_count + total);
     TRY(upload(e, e->d_fx_cls, fx->contrib_class, (size_t)std::max(total, 1), st));
     TRY(upload(e, e->d_fx_cnt, fx->contrib_count, (size_t)std::max(total, 1), st));
     e->fx_contrib = total > 0;
@@ -5084,6 +5090,260 @@ int32_t ykpred_headroom_spread_constraint(ykpred_engine_t* e, int32_t pod, uint3
   out[5] = c.min_domains;
   out[6] = c.self_match;
   out[7] = (int32_t)c.flags;
+  return YKPRED_OK;
+}
+
+// Does a spec QUALIFY for ykpred_headroom_affinity by its signature and the spec effects? InterPodAffinity is in both
+// lists (the call checked). → the status the host can decide — 0 candidate, 2 still coupled, 3 no InterPodAffinity constraint is live —
+// and, at 0: the signature, the topology key of the rows, the host's mode (0 static, 1 one per domain) and per row of the signature
+// whether an assumed pod of the spec adds to its selector class (*wmask, bit j = row j). Bootstrap is the fill kernel's to find.
+static int affinity_live_rows(const ykpred_engine* e, int32_t spec, uint32_t filt, int32_t* sig, int32_t* key, int32_t* mode, uint32_t* wmask) {
+  *sig = -1, *key = -1, *mode = 0, *wmask = 0;
+  if ((size_t)spec >= e->spec_sig_spread.size() || e->spec_sig_spread[(size_t)spec] < 0) return 3;
+  const int32_t d = e->spec_sig_spread[(size_t)spec];
+  const std::vector<ykpred_spread_t>& rows = e->spread_sig[(size_t)d];
+  const bool spread_en = filt & YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD;
+  bool spread_live = false;
+  int first = -1, star = -1;
+  bool two_keys = false;
+  for (size_t j = 0; j < rows.size(); ++j) {
+    const ykpred_spread_t& c = rows[j];
+    if (c.kind == ykk::kKindSpread) {
+      spread_live = spread_live || spread_en;
+      continue;
+    }
+    if (first < 0) first = (int)j;
+    int64_t w = 0;  // what one assumed pod of the spec adds to the row's selector class
+    if (c.selector_class >= 0 && (size_t)spec + 1 < e->h_fx_off.size())
+      for (int32_t r = e->h_fx_off[(size_t)spec]; r < e->h_fx_off[(size_t)spec + 1]; ++r)
+        if ((size_t)r < e->h_fx_cls.size() && e->h_fx_cls[(size_t)r] == c.selector_class) w += e->h_fx_cnt[(size_t)r];
+    if (w <= 0) continue;
+    if (j >= 32) return 2;  // (the mask holds 32 rows; a longer signature stays coupled)
+    *wmask |= 1u << j;
+    if (c.kind == ykk::kKindPodAntiAffinity || c.kind == ykk::kKindExistingAnti) {
+      if (star >= 0 && rows[(size_t)star].topology_key != c.topology_key) two_keys = true;
+      if (star < 0) star = (int)j;
+    }
+  }
+  if (spread_live) return 2;  // a SPREAD constraint beside the affinity ones (or alone: ykpred_headroom_spread answers)
+  if (first < 0) return 3;
+  if (two_keys) return 2;
+  *sig = d;
+  *mode = star >= 0 ? 1 : 0;
+  *key = rows[(size_t)(star >= 0 ? star : first)].topology_key;
+  return 0;
+}
+
+// Headroom of asks whose live topology constraints are InterPodAffinity's: k_headroom_affinity gathers cap / nodes per
+// domain of the task's key and in its outside row, k_affinity_fill decides bootstrap, derives the copies per domain and the summary. The
+// table is ragged — a task owns dom_size + 1 rows — and is worked through in TABLE CHUNKS under ykpred_headroom_groups' scratch budget;
+// a chunk's accumulation form follows from its largest dom_size. Both entry points run this routine; `rows` (may be null) receives the
+// [dom_size + 1][4] rows of the FIRST task when that task came out at status 0 or 4.
+extern "C++" {
+static int32_t headroom_affinity_run(ykpred_engine* e, const std::string& name, int32_t n_asks, const int32_t* asks, bool pointers_ok, uint32_t pre,
+                                     uint32_t filt, int64_t* out, std::vector<int64_t>* rows) {
+  static_assert(ykk::kAffHeadCells == YKPRED_AFFINITY_HEADROOM_CELLS, "k_affinity_fill writes the layout of ykpred.h");
+  constexpr size_t B = YKPRED_AFFINITY_HEADROOM_CELLS, RC = ykk::kSpreadRowCells;
+  constexpr int64_t kAffFillWideFrom = 4 * ykk::kWave;  // domains from which a task's fill gets the workgroup
+  auto more_checks = [&](std::string* why) -> int {
+    if (!(pre & filt & YKPRED_PLUGIN_INTER_POD_AFFINITY))
+      return *why = name + ": InterPodAffinity must be in both plugin lists (ykpred_headroom or ykpred_headroom_spread answers without it)", YKPRED_E_INVALID;
+    if (e->fx_version != e->specs_version)
+      return *why = name + ": the specs' effects are not uploaded for the current spec table (ykpred_set_spec_effects): what a copy adds to the histograms is unknown", YKPRED_E_UNSUPPORTED;
+    return YKPRED_OK;
+  };
+  u64 more = 0x9e3779b97f4a7c15ull;
+  more = (more ^ (u64)(uint32_t)e->group_scratch_mb) * 0x100000001b3ull;
+  more = (more ^ (u64)(uint32_t)e->group_chunk_tasks) * 0x100000001b3ull;
+  more = (more ^ (u64)(uint32_t)e->group_lds) * 0x100000001b3ull;
+  more = (more ^ (u64)(uint32_t)e->affinity_fill_waves) * 0x100000001b3ull;
+  more = (more ^ (u64)(e->fx_version == e->specs_version ? e->fx_version : 0)) * 0x100000001b3ull;  // (the effects every rank fills by)
+  HeadroomTasks tasks;
+  bool run = false;
+  const int32_t rc = headroom_prepare(e, name, n_asks, asks, pointers_ok, pre, filt, more_checks, more, &tasks, &run);
+  if (!run) return rc;
+  const bool sharded = e->comm && e->comm_world > 1;
+  hipStream_t st = e->own_stream;
+  if (e->spread_dirty) TRY(build_spread_tables(e, st));
+  const size_t T = tasks.spec.size();
+  std::vector<ykk::AffHeadTask> ht(T);
+  std::vector<int64_t> t_rows(T, 0);  // table rows of the task: its domains and the outside row, none when it does not qualify
+  for (size_t k = 0; k < T; ++k) {
+    ykk::AffHeadTask& h = ht[k];
+    h = ykk::AffHeadTask{tasks.spec[k], tasks.pin[k], -1, -1, 0, 0, 2, 0u, 0};
+    int32_t d = -1, key = -1, mode = 0;
+    uint32_t wmask = 0;
+    h.status = affinity_live_rows(e, tasks.spec[k], filt, &d, &key, &mode, &wmask);
+    if (h.status != 0) continue;
+    h.sig = d, h.kd = key, h.mode = mode, h.wmask = wmask;
+    h.dom_size = (size_t)key < e->h_domain_sizes.size() ? e->h_domain_sizes[(size_t)key] : 0;
+    t_rows[k] = (int64_t)h.dom_size + 1;
+  }
+  std::vector<int64_t> sums(T * B, 0);
+  if (e->N == 0 && !sharded) {
+    // (no node: no histogram was built and no kernel runs. No pod matches anywhere, so a self-matching, self-contributing affinity row
+    // is in bootstrap: the fill's rule on the host. A shard without nodes of a sharded engine takes the other branch)
+    for (size_t k = 0; k < T; ++k) {
+      int64_t* row = sums.data() + k * B;
+      const bool routed = (size_t)ht[k].spec < e->h_sflags.size() && (e->h_sflags[(size_t)ht[k].spec] & YKPRED_SPEC_UNSUPPORTED);
+      int status = routed ? 1 : ht[k].status, mode = ht[k].mode;
+      if (status == 0) {
+        const std::vector<ykpred_spread_t>& sr = e->spread_sig[(size_t)ht[k].sig];
+        int n_aff = 0;
+        bool candidate = false;
+        for (size_t j = 0; j < sr.size(); ++j)
+          if (sr[j].kind == ykk::kKindPodAffinity) ++n_aff, candidate = candidate || (sr[j].self_match != 0 && j < 32 && ((ht[k].wmask >> j) & 1u));
+        if (candidate) {
+          if (n_aff == 1 && mode == 0) status = 4, mode = 2;
+          else status = 2;
+        }
+      }
+      row[3] = status;
+      if (status == 2) row[0] = row[2] = -1;
+      if (status == 0 || status == 4) {
+        if (status == 4) row[0] = -1;
+        row[11] = -1;
+        row[12] = ht[k].kd;
+        row[13] = mode;
+      }
+    }
+    if (rows) rows->clear();
+  } else {
+    // Table chunks: consecutive tasks while their rows fit the budget (at least one task; group_chunk_tasks overrides the count).
+    const size_t budget = (size_t)e->group_scratch_mb << 20;
+    std::vector<size_t> chunk_begin{0};
+    size_t biggest = 0;
+    {
+      size_t bytes = 0, count = 0;
+      for (size_t k = 0; k < T; ++k) {
+        const size_t need = ((size_t)t_rows[k] * RC + 1) * sizeof(int64_t);
+        const bool full = e->group_chunk_tasks > 0 ? count >= (size_t)e->group_chunk_tasks : (count > 0 && bytes + need > budget);
+        if (full) {
+          chunk_begin.push_back(k);
+          bytes = 0, count = 0;
+        }
+        bytes += need;
+        ++count;
+        biggest = std::max(biggest, bytes);
+      }
+      chunk_begin.push_back(T);
+    }
+    auto up8 = [](size_t b) { return (b + 7) & ~(size_t)7; };
+    const size_t o_tasks = T * B * sizeof(int64_t), o_table = up8(o_tasks + T * sizeof(ykk::AffHeadTask));
+    HIPCHK(e->d_aff_head.ensure(o_table + biggest + 64));
+    char* base = e->d_aff_head.as<char>();
+    int64_t* d_summary = (int64_t*)base;
+    ykk::AffHeadTask* d_tasks = (ykk::AffHeadTask*)(base + o_tasks);
+    int64_t* d_table = (int64_t*)(base + o_table);
+    // (row0 counts from the start of the task's chunk)
+    for (size_t ci = 0; ci + 1 < chunk_begin.size(); ++ci) {
+      int64_t at = 0;
+      for (size_t k = chunk_begin[ci]; k < chunk_begin[ci + 1]; ++k) ht[k].row0 = at, at += t_rows[k];
+    }
+    HIPCHK(hipMemcpyAsync(d_tasks, ht.data(), T * sizeof(ykk::AffHeadTask), hipMemcpyHostToDevice, st));
+    for (size_t ci = 0; ci + 1 < chunk_begin.size(); ++ci) {
+      const size_t c0 = chunk_begin[ci], tc = chunk_begin[ci + 1] - c0;
+      size_t n_rows = 0;
+      int64_t widest = 0;
+      for (size_t k = c0; k < c0 + tc; ++k) n_rows += (size_t)t_rows[k], widest = std::max(widest, (int64_t)ht[k].dom_size);
+      int64_t* d_unsupported = d_table + n_rows * RC;
+      const size_t cells = n_rows * RC + tc;
+      HIPCHK(hipMemsetAsync(d_table, 0, cells * sizeof(int64_t), st));
+      const dim3 grid((unsigned)((tc + ykk::kExplainTasks - 1) / ykk::kExplainTasks), (unsigned)(((size_t)e->N + ykk::kBlock - 1) / ykk::kBlock));
+      if (e->N == 0) {
+      } else if (widest <= ykk::kGroupLdsMaxGroups && e->group_lds != 0)
+        hipLaunchKernelGGL(ykk::k_headroom_affinity<true>, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e), (int)tc, d_tasks + c0, pre, filt,
+                           (ykk::i64*)d_table, (ykk::i64*)d_unsupported);
+      else
+        hipLaunchKernelGGL(ykk::k_headroom_affinity<false>, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e), (int)tc, d_tasks + c0, pre, filt,
+                           (ykk::i64*)d_table, (ykk::i64*)d_unsupported);
+      HIPCHK(hipGetLastError());
+      if (sharded) NCCLCHK(rccl()->AllReduce(d_table, d_table, cells, ncclInt64, ncclSum, e->comm, st));
+      const bool wide = e->affinity_fill_waves > 0 ? e->affinity_fill_waves > 1 : widest >= kAffFillWideFrom;
+      if (wide)
+        hipLaunchKernelGGL(ykk::k_affinity_fill<ykk::kWavesPerBlock>, dim3((unsigned)tc), dim3(ykk::kBlock), 0, st, (int)tc, d_tasks + c0, spread_sigs(e),
+                           (ykk::i64*)d_table, (const ykk::i64*)d_unsupported, (ykk::i64*)(d_summary + c0 * B));
+      else
+        hipLaunchKernelGGL(ykk::k_affinity_fill<1>, dim3((unsigned)((tc + ykk::kWavesPerBlock - 1) / ykk::kWavesPerBlock)), dim3(ykk::kBlock), 0, st, (int)tc,
+                           d_tasks + c0, spread_sigs(e), (ykk::i64*)d_table, (const ykk::i64*)d_unsupported, (ykk::i64*)(d_summary + c0 * B));
+      HIPCHK(hipGetLastError());
+      if (rows && ci == 0) {
+        rows->assign((size_t)t_rows[0] * RC, 0);
+        if (!rows->empty()) HIPCHK(hipMemcpyAsync(rows->data(), d_table, rows->size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+      }
+      // (the next chunk reuses the table: the stream orders its fill behind this chunk's kernels and copy)
+    }
+    HIPCHK(hipMemcpyAsync(sums.data(), d_summary, T * B * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  for (int i = 0; i < n_asks; ++i) memcpy(out + (size_t)i * B, sums.data() + (size_t)tasks.task_of[(size_t)i] * B, B * sizeof(int64_t));
+  return YKPRED_OK;
+}
+}  // extern "C++"
+
+int32_t ykpred_headroom_affinity(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, uint32_t pre, uint32_t filt, int64_t* out) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:headroom_affinity");
+  if (e) e->n_queries++;
+  if (!e) return YKPRED_E_INVALID;
+  return headroom_affinity_run(e, "headroom_affinity", n_asks, asks, n_asks <= 0 || (asks && out), pre, filt, out, nullptr);
+}
+
+// The per-domain rows behind one ask's summary, the outside row last. On a sharded engine the whole computation is the collective one of
+// ykpred_headroom_affinity; the argument checks that only this rank can fail come after it.
+int32_t ykpred_headroom_affinity_pod(ykpred_engine_t* e, int32_t pod, uint32_t pre, uint32_t filt, int32_t max_domains, int64_t* out,
+                                     int32_t* num_domains) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:headroom_affinity_pod");
+  if (e) e->n_queries++;
+  if (!e) return YKPRED_E_INVALID;
+  int64_t cells[YKPRED_AFFINITY_HEADROOM_CELLS];
+  std::vector<int64_t> rows;
+  const int32_t rc = headroom_affinity_run(e, "headroom_affinity_pod", 1, &pod, num_domains != nullptr && max_domains >= 0 && out != nullptr, pre, filt,
+                                           cells, &rows);
+  if (rc != YKPRED_OK) return rc;
+  if (cells[3] != 0 && cells[3] != 4)
+    return fail(e, YKPRED_E_UNSUPPORTED, "headroom_affinity_pod: the ask is at status " + std::to_string((long long)cells[3]) + " (ykpred_headroom_affinity): it has no per-domain rows");
+  const size_t D = rows.empty() ? 0 : rows.size() / ykk::kSpreadRowCells - 1;
+  *num_domains = (int32_t)D;
+  if ((size_t)max_domains < D) return fail(e, YKPRED_E_INVALID, "headroom_affinity_pod: out holds fewer than " + std::to_string(D) + " domains and the outside row");
+  std::fill(out, out + (D + 1) * ykk::kSpreadRowCells, (int64_t)0);  // (no node: no table, every row 0)
+  if (!rows.empty()) memcpy(out, rows.data(), rows.size() * sizeof(int64_t));
+  return YKPRED_OK;
+}
+
+// Where the live anti rows on an ask's key lie in the topology histograms (layout.spread_counts): what a host needs to read the cells
+// ykpred_headroom_affinity sums into cnt. Tables and effects only; no launch, nothing exchanged.
+int32_t ykpred_headroom_affinity_constraint(ykpred_engine_t* e, int32_t pod, uint32_t pre, uint32_t filt, int32_t* out) {
+  YK_SERIALISE(e);
+  if (!e || !out) return fail(e, YKPRED_E_INVALID, "headroom_affinity_constraint: bad argument");
+  if (!e->nodes_set || !e->specs_set || !e->pods_set) return fail(e, YKPRED_E_STATE, "headroom_affinity_constraint: tables not uploaded");
+  if (pod < 0 || pod >= e->P) return fail(e, YKPRED_E_INVALID, "headroom_affinity_constraint: index out of range");
+  if (!(pre & filt & YKPRED_PLUGIN_INTER_POD_AFFINITY)) return fail(e, YKPRED_E_INVALID, "headroom_affinity_constraint: InterPodAffinity must be in both plugin lists");
+  if (e->fx_version != e->specs_version) return fail(e, YKPRED_E_UNSUPPORTED, "headroom_affinity_constraint: the specs' effects are not uploaded for the current spec table (ykpred_set_spec_effects)");
+  std::fill(out, out + YKPRED_AFFINITY_CONSTRAINT_CELLS, (int32_t)0);
+  const int32_t spec = e->h_pod_spec[(size_t)pod];
+  int32_t d = -1, key = -1, mode = 0;
+  uint32_t wmask = 0;
+  out[0] = affinity_live_rows(e, spec, filt, &d, &key, &mode, &wmask);
+  if ((size_t)spec < e->h_sflags.size() && (e->h_sflags[(size_t)spec] & YKPRED_SPEC_UNSUPPORTED)) out[0] = 1;
+  if (out[0] != 0) return YKPRED_OK;
+  out[1] = key;
+  out[2] = mode;
+  out[3] = (size_t)key < e->h_domain_sizes.size() ? e->h_domain_sizes[(size_t)key] : 0;
+  int64_t off = 0;  // (the cell ranges build_spread_tables assigns: constraint after constraint, signature after signature)
+  int found = 0;
+  for (int32_t dd = 0; dd <= d; ++dd)
+    for (size_t j = 0; j < e->spread_sig[(size_t)dd].size(); ++j) {
+      const ykpred_spread_t& c = e->spread_sig[(size_t)dd][j];
+      const bool anti = c.kind == ykk::kKindPodAntiAffinity || c.kind == ykk::kKindExistingAnti;
+      if (dd == d && anti && c.topology_key == key) {
+        if (found < YKPRED_AFFINITY_CONSTRAINT_ROWS) out[5 + found] = (int32_t)off;
+        ++found;
+      }
+      off += (size_t)c.topology_key < e->h_domain_sizes.size() ? e->h_domain_sizes[(size_t)c.topology_key] : 0;
+    }
+  out[4] = found;
   return YKPRED_OK;
 }
 

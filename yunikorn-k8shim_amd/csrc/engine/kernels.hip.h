@@ -3355,6 +3355,205 @@ __global__ __launch_bounds__(kBlock) void k_spread_fill(int n_tasks, const Sprea
   }
 }
 
+// ykpred_headroom_affinity: headroom of an ask whose live topology constraints are all of the InterPodAffinity kinds.
+// Copies then interact only through the histogram rows of the anti-affinity terms they themselves add to, all on ONE topology key (the
+// host decides that from the signature tables and the spec effects), and the sequential loop over copies has a closed result per DOMAIN
+// of that key. This kernel gathers its inputs: table[row0 + d] = { cnt, cap, nodes, copies } per domain d of the task's key, of which it
+// adds cap = Σ replicas over the nodes of the domain and nodes = how many of them take a copy; replicas is ykpred_headroom's routine
+// under the caller's lists, InterPodAffinity included: the pair's verdict is the static one against the current histograms. A node
+// WITHOUT the key is not dropped — an anti-affinity row passes it and a copy placed there moves no cell — it adds to the task's OUTSIDE
+// row, table[row0 + dom_size]. Grid and walk of k_headroom_spread: blockIdx.x = chunk of kExplainTasks tasks, blockIdx.y = 256 nodes,
+// lane = node; node columns once per chunk, task data wave-uniform, a wave in which no lane fits skips the task; the lane's domain id is
+// the resident NodeRegs.dom. Two accumulation forms:
+//   use_lds  every task of the launch has dom_size <= kGroupLdsMaxGroups: the chunk's [kExplainTasks][kSpreadLdsRows][2] cells live in
+//            LDS, row kGroupLdsMaxGroups of a task serving as its outside row; the block flushes its non-zero cells with one global
+//            integer add each;
+//   else     the adds go straight to the global table.
+// Integer adds only: the result does not depend on the order of arrival. A task with kd < 0 does not qualify by its signature and is
+// skipped. unsupported[task] = 1 for a spec the engine does not evaluate (first node group alone).
+struct AffHeadTask {
+  int spec, pin;   // the task
+  int sig, kd;     // its topology signature and the topology key its rows lie on; kd = -1: does not qualify, no rows
+  i64 row0;        // first row of the task in the chunk's table; it owns dom_size + 1 rows, the last one for nodes without the key
+  int dom_size;    // domains of key kd
+  int status;      // the host's verdict: 0 computed unless the fill objects, 2 still coupled, 3 no InterPodAffinity constraint is live
+  unsigned wmask;  // bit j: an assumed pod of the spec adds to the selector class of row j of the signature (w > 0)
+  int mode;        // the host's: 0 static, 1 one per domain (some self-contributing anti row); the fill may find 2, bootstrap
+};
+constexpr int kAffHeadCells = 16;
+template <bool use_lds>
+__global__ __launch_bounds__(kBlock) void k_headroom_affinity(NodeTable t, SpecTable s, int n_tasks, const AffHeadTask* __restrict__ tasks,
+                                                              unsigned pre_mask, unsigned filt_mask, i64* __restrict__ table,
+                                                              i64* __restrict__ unsupported) {
+  __shared__ i64 sacc[use_lds ? kExplainTasks * kSpreadLdsRows * 2 : 1];
+  const int k0 = blockIdx.x * kExplainTasks, kend = min(k0 + kExplainTasks, n_tasks);
+  if (use_lds) {
+    for (int i = threadIdx.x; i < (kend - k0) * kSpreadLdsRows * 2; i += kBlock) sacc[i] = 0;
+    __syncthreads();
+  }
+  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+  int n = (blockIdx.y * kWavesPerBlock + wave) * kWave + lane;
+  const bool live = n < t.n;
+  if (!live) n = -1;
+  if (__ballot(live)) {  // (wave-uniform: a wave wholly past N skips the walk, not the barriers)
+    NodeRegs nr;
+    load_node(t, n, &nr);
+    const i64 slots = live ? (i64)t.allowed[n] - (i64)t.count[n] : 0;
+    for (int k = k0; k < kend; ++k) {
+      const AffHeadTask tk = tasks[k];
+      if (tk.kd < 0) continue;  // (wave-uniform)
+      int binder = 0;
+      const int rep = live ? replicas(s, tk.spec, tk.pin, n, nr, slots, pre_mask, filt_mask, &binder) : 0;
+      if (!__ballot(rep > 0)) continue;  // (wave-uniform: no lane fits)
+      if (rep <= 0) continue;
+      int dm = -1;
+#pragma unroll
+      for (int kd = 0; kd < kMaxKD; ++kd)
+        if (kd == tk.kd) dm = nr.dom[kd];
+      const bool inside = dm >= 0 && dm < tk.dom_size;
+      if (use_lds) {
+        i64* cell = sacc + ((k - k0) * kSpreadLdsRows + (inside ? dm : kGroupLdsMaxGroups)) * 2;
+        atomicAdd((u64*)&cell[0], (u64)rep);
+        atomicAdd((u64*)&cell[1], (u64)1);
+      } else {
+        i64* cell = table + ((size_t)tk.row0 + (inside ? dm : tk.dom_size)) * kSpreadRowCells;
+        atomicAdd((u64*)&cell[1], (u64)rep);
+        atomicAdd((u64*)&cell[2], (u64)1);
+      }
+    }
+  }
+  if (use_lds) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < (kend - k0) * kSpreadLdsRows * 2; i += kBlock) {
+      const i64 v = sacc[i];  // (non-zero only in rows below the task's dom_size and in its outside row)
+      if (!v) continue;
+      const AffHeadTask tk = tasks[k0 + i / (kSpreadLdsRows * 2)];
+      const int r = (i / 2) % kSpreadLdsRows;
+      atomicAdd((u64*)&table[((size_t)tk.row0 + (r == kGroupLdsMaxGroups ? tk.dom_size : r)) * kSpreadRowCells + 1 + (i & 1)], (u64)v);
+    }
+  }
+  if (blockIdx.y == 0 && (int)threadIdx.x < kend - k0 && (s.flags[tasks[k0 + threadIdx.x].spec] & kSpecUnsupported)) unsupported[k0 + threadIdx.x] = 1;
+}
+
+// The fill of one task over its domain rows after the table is complete (on a sharded engine: after the all-reduce; the histograms are
+// cluster-wide already, so every rank derives the same rows). W waves share a task: W = 1 puts kWavesPerBlock tasks in a block and needs
+// no barrier; W = kWavesPerBlock gives the task the whole workgroup, which meets in LDS — the form for one domain per node, where one
+// wave's scan of 50 000 rows is the call. Thread i of the task scans domains i, i + 64 W, ... ascending:
+//   cnt(d)    = Σ over the anti-affinity and existing-anti-affinity rows of the signature on the task's key of their histogram cell
+//   copies(d) = cap(d) in mode 0, min(cap(d), 1) in mode 1; the outside row keeps its cap in either
+// BOOTSTRAP is decided here, from the cluster-wide minv: some affinity row matches the spec itself, an assumed copy adds to it, and no
+// pod matches anywhere (Σ minv over the affinity rows == 0, the escape of constraints_fail). The first copy may then land anywhere and
+// pins its domain: with exactly one affinity row and no self-contributing anti row (mode 0 by the host) the task comes out at status 4,
+// mode 2, copies(d) = cap(d) = "what the gang gets if it starts here", [0] = -1; any other bootstrap is status 2. Every comparison of
+// the reduction is total — (value, id) — so the result is deterministic. Cells: include/ykpred.h, YKPRED_AFFINITY_HEADROOM_CELLS.
+template <int W>
+__global__ __launch_bounds__(kBlock) void k_affinity_fill(int n_tasks, const AffHeadTask* __restrict__ tasks, SpreadSigs sp, i64* __restrict__ table,
+                                                          const i64* __restrict__ unsupported, i64* __restrict__ summary) {
+  static_assert(W == 1 || W == kWavesPerBlock, "a wave or the workgroup per task");
+  __shared__ i64 red64[W > 1 ? W * 4 : 1];
+  __shared__ int red32[W > 1 ? W * 5 : 1];
+  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+  const int k = blockIdx.x * (kWavesPerBlock / W) + wave / W, sub = wave % W;
+  if (k >= n_tasks) return;  // (W == 1: wave-uniform and no barrier below; else block-uniform)
+  const AffHeadTask tk = tasks[k];
+  i64* out = summary + (size_t)k * kAffHeadCells;
+  int status = unsupported[k] != 0 ? 1 : tk.status;
+  int mode = tk.mode;
+  const int g0 = tk.sig >= 0 ? sp.c_off[tk.sig] : 0, g1 = tk.sig >= 0 ? sp.c_off[tk.sig + 1] : 0;
+  if (status == 0) {  // (uniform over the task's threads: they read the same rows)
+    int n_aff = 0;
+    i64 matches = 0;
+    bool candidate = false;
+    for (int g = g0; g < g1; ++g) {
+      const SpreadC c = sp.c[g];
+      if (c.kind != kKindPodAffinity) continue;
+      ++n_aff;
+      matches += sp.minv[g];
+      candidate = candidate || (c.self_match != 0 && g - g0 < 32 && ((tk.wmask >> (g - g0)) & 1u));
+    }
+    if (candidate && matches == 0) {
+      if (n_aff == 1 && tk.mode == 0) status = 4, mode = 2;
+      else status = 2;
+    }
+  }
+  if (status != 0 && status != 4) {
+    if (sub == 0 && lane < kAffHeadCells) out[lane] = lane == 3 ? status : (status == 2 && (lane == 0 || lane == 2)) ? -1 : 0;
+    return;
+  }
+  i64* row = table + (size_t)tk.row0 * kSpreadRowCells;
+  i64 sum = 0, most = 0, caps = 0, nodes = 0;
+  int some = 0, best = -1, filled = 0, cut = 0, blocked = 0;
+  for (int d = sub * kWave + lane; d < tk.dom_size; d += W * kWave) {
+    i64 cnt = 0;
+    for (int g = g0; g < g1; ++g) {
+      const SpreadC c = sp.c[g];
+      if ((c.kind == kKindPodAntiAffinity || c.kind == kKindExistingAnti) && c.kd == tk.kd && d < c.dom_size) cnt += sp.cnt[c.cnt_off + d];
+    }
+    const i64 cap = row[d * kSpreadRowCells + 1];
+    const i64 cp = mode == 1 ? min(cap, (i64)1) : cap;
+    row[d * kSpreadRowCells] = cnt;
+    row[d * kSpreadRowCells + 3] = cp;
+    sum += cp;
+    caps += cap;
+    nodes += row[d * kSpreadRowCells + 2];
+    some += cp >= 1;
+    blocked += cnt > 0;
+    if (cp > most) most = cp, best = d;
+    filled += cap >= 1 && cp == cap;
+    cut += cp > 0 && cp < cap;
+  }
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) {
+    sum += (i64)__shfl_xor((long long)sum, off, kWave);
+    caps += (i64)__shfl_xor((long long)caps, off, kWave);
+    nodes += (i64)__shfl_xor((long long)nodes, off, kWave);
+    some += __shfl_xor(some, off, kWave);
+    blocked += __shfl_xor(blocked, off, kWave);
+    filled += __shfl_xor(filled, off, kWave);
+    cut += __shfl_xor(cut, off, kWave);
+    const i64 omost = (i64)__shfl_xor((long long)most, off, kWave);
+    const int obest = __shfl_xor(best, off, kWave);
+    if (obest >= 0 && (best < 0 || omost > most || (omost == most && obest < best))) most = omost, best = obest;
+  }
+  if (W > 1) {  // the task's waves meet in LDS; its first wave combines them in wave order
+    if (lane == 0) {
+      red64[sub * 4] = sum, red64[sub * 4 + 1] = caps, red64[sub * 4 + 2] = nodes, red64[sub * 4 + 3] = most;
+      red32[sub * 5] = some, red32[sub * 5 + 1] = blocked, red32[sub * 5 + 2] = filled, red32[sub * 5 + 3] = cut, red32[sub * 5 + 4] = best;
+    }
+    __syncthreads();
+    if (sub != 0) return;
+    for (int w = 1; w < W; ++w) {
+      sum += red64[w * 4], caps += red64[w * 4 + 1], nodes += red64[w * 4 + 2];
+      some += red32[w * 5], blocked += red32[w * 5 + 1], filled += red32[w * 5 + 2], cut += red32[w * 5 + 3];
+      const i64 omost = red64[w * 4 + 3];
+      const int obest = red32[w * 5 + 4];
+      if (obest >= 0 && (best < 0 || omost > most || (omost == most && obest < best))) most = omost, best = obest;
+    }
+  }
+  if (lane == 0) {
+    i64* outside = row + (size_t)tk.dom_size * kSpreadRowCells;
+    const i64 cap_out = outside[1], nodes_out = outside[2];
+    outside[0] = 0;
+    outside[3] = cap_out;
+    out[0] = status == 4 ? -1 : sum + cap_out;
+    out[1] = some;
+    out[2] = best < 0 ? 0 : most;
+    out[3] = status;
+    out[4] = caps;
+    out[5] = blocked;
+    out[6] = cap_out;
+    out[7] = nodes_out;
+    out[8] = filled;
+    out[9] = cut;
+    out[10] = 0;
+    out[11] = best;
+    out[12] = tk.kd;
+    out[13] = mode;
+    out[14] = nodes + nodes_out;
+    out[15] = 0;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // incremental column patch: only the bitmap columns of the listed (updated) nodes are re-evaluated
 // ---------------------------------------------------------------------------------------------------

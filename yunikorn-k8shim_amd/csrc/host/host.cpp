@@ -2954,9 +2954,11 @@ int32_t ykhost_candidates(ykhost_t* h, int32_t pod, int32_t allocate, int32_t k,
 // What AssumePod of an ask adds to its node besides its resources — the selector-class counts behind PodTopologySpread /
 // InterPodAffinity and the host ports it occupies — per spec, so that the device round can keep that state current ask by ask
 // (ykpred_set_spec_effects). Only a round needs it: built and uploaded on the first round after the spec table moved.
-static int upload_spec_effects(ykhost* h) {
+// `always`: also when nothing but resources couples the asks (ykpred_headroom_affinity asks for effects of the current spec table whatever
+// they hold).
+static int upload_spec_effects(ykhost* h, bool always = false) {
   if (h->fx_uploaded) return 0;
-  if (h->enc.KS == 0 && h->enc.KP == 0) return 0;  // nothing but resources couples the asks
+  if (h->enc.KS == 0 && h->enc.KP == 0 && !always) return 0;  // nothing but resources couples the asks
   std::vector<int32_t> off, cls, cnt;
   std::vector<uint64_t> occupied;
   h->enc.spec_effects(h->spec_templates, &off, &cls, &cnt, &occupied);
@@ -3707,6 +3709,97 @@ int32_t ykhost_headroom_spread_by_key(ykhost_t* h, const char* allocation_key, i
   rc = ykhost_headroom_spread(h, 1, &row, out16);
   if (rc) return rc;
   if (out16[3] == 0 && out16[11] >= 0) {
+    const std::vector<std::string> names = spread_domain_values(h, out16[12]);
+    if ((size_t)out16[11] < names.size()) copy_out(names[(size_t)out16[11]], best, best_len);
+  }
+  return 0;
+}
+
+// ---- headroom of asks with required pod (anti-)affinity (ykpred_headroom_affinity) -------------------------------------------------------
+// The other fallback when ykhost_headroom reports an ask as coupled. Always the ALLOCATION-phase plugin lists. What a copy adds to the
+// histograms comes from the spec effects: uploaded here when the spec table moved since the last upload.
+int32_t ykhost_headroom_affinity(ykhost_t* h, int32_t n, const int32_t* asks, int64_t* out_cells) {
+  YKHOST_LOCKED(h);
+  if (n < 0 || (n > 0 && !out_cells)) return fail(h, "headroom_affinity: bad argument", -1);
+  if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
+  int rc = sync(h);
+  if (rc) return rc;
+  rc = upload_spec_effects(h, true);
+  if (rc) return rc;
+  int32_t world = 1;
+  ykpred_comm_info(h->eng, nullptr, &world, nullptr);
+  const int P = (int)h->pending.size();
+  // (on a node-sharded handle the engine checks the indices: its agreement step gives every rank the same error)
+  if (world <= 1)
+    for (int i = 0; i < n; ++i)
+      if ((asks ? asks[i] : i) < 0 || (asks ? asks[i] : i) >= P) return fail(h, "headroom_affinity: ask index out of range", YKPRED_E_INVALID);
+  std::vector<int32_t> list, slot;
+  for (int i = 0; i < n; ++i) {
+    const int row = asks ? asks[i] : i;
+    int64_t* c = out_cells + (size_t)i * YKPRED_AFFINITY_HEADROOM_CELLS;
+    if (world <= 1 && h->enc.unsupported.count(h->pending[(size_t)row]->tpl)) {  // routed: status 1 without a device call
+      std::fill(c, c + YKPRED_AFFINITY_HEADROOM_CELLS, (int64_t)0);
+      c[3] = 1;
+    } else {
+      list.push_back(row);
+      slot.push_back(i);
+    }
+  }
+  if (list.empty() && world <= 1) return 0;
+  std::vector<int64_t> rows(list.size() * (size_t)YKPRED_AFFINITY_HEADROOM_CELLS);
+  rc = ykpred_headroom_affinity(h->eng, (int32_t)list.size(), list.data(), h->alloc_pre, h->alloc_filt, rows.data());
+  if (rc) return fail(h, std::string("ykpred_headroom_affinity: ") + ykpred_last_error(h->eng), rc);
+  for (size_t k = 0; k < list.size(); ++k)
+    memcpy(out_cells + (size_t)slot[k] * YKPRED_AFFINITY_HEADROOM_CELLS, rows.data() + k * YKPRED_AFFINITY_HEADROOM_CELLS,
+           YKPRED_AFFINITY_HEADROOM_CELLS * sizeof(int64_t));
+  return 0;
+}
+
+int32_t ykhost_headroom_affinity_domains(ykhost_t* h, int32_t pod, int64_t* out_summary, int64_t* out_rows, int32_t max_domains, char* values,
+                                         int64_t values_len) {
+  YKHOST_LOCKED(h);
+  if (!out_summary || max_domains < 0 || !out_rows) return fail(h, "headroom_affinity_domains: bad argument", -1);
+  copy_out("[]", values, values_len);
+  int rc = ykhost_headroom_affinity(h, 1, &pod, out_summary);
+  if (rc) return rc;
+  if (out_summary[3] != 0 && out_summary[3] != 4) return 0;
+  int32_t D = 0;
+  rc = ykpred_headroom_affinity_pod(h->eng, pod, h->alloc_pre, h->alloc_filt, max_domains, out_rows, &D);
+  if (rc == YKPRED_E_INVALID && D > max_domains) return D;  // (the size needed, as ykhost_explain_format reports a length)
+  if (rc) return fail(h, std::string("ykpred_headroom_affinity_pod: ") + ykpred_last_error(h->eng), rc);
+  const std::vector<std::string> names = spread_domain_values(h, out_summary[12]);
+  std::string o = "[";
+  for (int32_t d = 0; d < D; ++d) {
+    if (d) o += ',';
+    js_str(o, (size_t)d < names.size() ? names[(size_t)d] : std::string());
+  }
+  o += ']';
+  copy_out(o, values, values_len);
+  return D;
+}
+
+// One ask named as the core names it, one crossing: the summary and the domain with the most copies as a label value.
+int32_t ykhost_headroom_affinity_by_key(ykhost_t* h, const char* allocation_key, int64_t* out16, char* best, int64_t best_len) {
+  YKHOST_LOCKED(h);
+  if (!out16) return fail(h, "headroom_affinity_by_key: bad argument", -1);
+  std::fill(out16, out16 + YKPRED_AFFINITY_HEADROOM_CELLS, (int64_t)0);
+  copy_out("", best, best_len);
+  ensure_uid_index(h);
+  auto it = h->by_uid.find(allocation_key ? allocation_key : "");
+  if (it == h->by_uid.end()) return YKHOST_E_POD_NOT_FOUND;
+  if (!it->second->ask) return fail(h, "pod holds no ask row", YKHOST_E_NOT_AN_ASK);
+  if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
+  int rc = sync(h);
+  if (rc) return rc;
+  auto un = h->enc.unsupported.find(it->second->tpl);
+  if (un != h->enc.unsupported.end()) {
+    out16[3] = 1;
+    return fail(h, "ask is not evaluated by the engine (route it to the CPU predicate manager): " + un->second, YKHOST_E_UNSUPPORTED);
+  }
+  const int32_t row = it->second->row;
+  rc = ykhost_headroom_affinity(h, 1, &row, out16);
+  if (rc) return rc;
+  if ((out16[3] == 0 || out16[3] == 4) && out16[11] >= 0) {
     const std::vector<std::string> names = spread_domain_values(h, out16[12]);
     if ((size_t)out16[11] < names.size()) copy_out(names[(size_t)out16[11]], best, best_len);
   }

@@ -49,6 +49,11 @@ GROUP_CELLS, GROUP_SUMMARY, GROUP_LDS_MAX_GROUPS = 2, 8, 63
 # filled / cut / shut, the domain with the most copies, topology key index, maxSkew, fitting nodes, 0; per (ask, domain)
 # int64[SPREAD_ROW_CELLS] = cnt, cap, nodes, copies
 SPREAD_HEADROOM_CELLS, SPREAD_ROW_CELLS = 16, 4
+# ykpred_headroom_affinity: per ask int64[AFFINITY_HEADROOM_CELLS] = copies (outside included), domains with a copy, most copies in a
+# domain, status (0 computed, 1 routed, 2 still coupled, 3 no InterPodAffinity constraint is live, 4 bootstrap), sum of cap, blocked
+# domains, copies outside, nodes outside, domains filled / cut, 0, the domain with the most copies, topology key index, mode (0 static,
+# 1 one per domain, 2 bootstrap), fitting nodes, 0; per (ask, domain) int64[SPREAD_ROW_CELLS] = cnt, cap, nodes, copies
+AFFINITY_HEADROOM_CELLS = 16
 
 
 def plugin_mask(names):
@@ -819,6 +824,77 @@ class GpuPredicateManager:
         rows = np.zeros((max(int(where[3]), 1), SPREAD_ROW_CELLS), dtype=np.int64)
         self._pcheck(self._P.ykpred_headroom_spread_pod(self.engine, p, pre, filt, len(rows), rows.ctypes.data, C.byref(count)))
         return cells, rows[:count.value].copy(), None
+
+    def headroom_affinity(self, pods=None, pre_mask=None, filt_mask=None):
+        """Headroom of asks with required pod (anti-)affinity (ykpred_headroom_affinity) — "one executor per host" and its kin, which
+        headroom() reports as coupled: np.int64[n, AFFINITY_HEADROOM_CELLS]. pods: ask indices or UIDs in any order, repeats allowed;
+        None = every ask. Allocation-phase lists; explicit masks go to the engine directly (the spec effects must then be uploaded:
+        any call with the default lists does that). Needs no evaluation and disturbs none. [3] is the status: 0 computed, 1 routed,
+        2 still coupled (total = max = -1), 3 no inter-pod affinity constraint is live, 4 bootstrap (total = -1, per-domain rows valid)."""
+        if pods is None:
+            count, ptr = self.num_pods, None
+        else:
+            idx = [p if isinstance(p, (int, np.integer)) else self.pod_index(p) for p in pods]
+            arr = np.ascontiguousarray(idx, dtype=np.int32)
+            count, ptr = len(arr), arr.ctypes.data
+        out = np.zeros((max(count, 1), AFFINITY_HEADROOM_CELLS), dtype=np.int64)
+        if pre_mask is None and filt_mask is None:
+            self._check(self._L.ykhost_headroom_affinity(self._h, count, ptr, out.ctypes.data))
+        else:
+            self._check(self._L.ykhost_headroom_affinity(self._h, 0, None, None))  # (an empty list: syncs and uploads the spec effects)
+            pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
+            if ptr is None:
+                arr = np.arange(count, dtype=np.int32)
+                ptr = arr.ctypes.data
+            self._pcheck(self._P.ykpred_headroom_affinity(self.engine, count, ptr, pre, filt, out.ctypes.data))
+        return out[:count].copy()
+
+    def headroom_affinity_domains(self, pod, pre_mask=None, filt_mask=None):
+        """The per-domain rows behind headroom_affinity for ONE ask (index or UID): (cells np.int64[AFFINITY_HEADROOM_CELLS], rows
+        np.int64[D + 1, SPREAD_ROW_CELLS] = cnt, cap, nodes, copies per domain of the ask's key with the OUTSIDE row — the nodes without
+        the key — last, values) — values are the domains' label values in id order (None with explicit masks, which go to the engine
+        directly). At a status other than 0 and 4 the rows are empty."""
+        p = int(pod if isinstance(pod, (int, np.integer)) else self.pod_index(pod))
+        cells = np.zeros(AFFINITY_HEADROOM_CELLS, dtype=np.int64)
+        if pre_mask is None and filt_mask is None:
+            cap, vlen = 64, 4096
+            while True:
+                rows = np.zeros((cap + 1, SPREAD_ROW_CELLS), dtype=np.int64)
+                buf = C.create_string_buffer(vlen)
+                rc = self._check(self._L.ykhost_headroom_affinity_domains(self._h, p, cells.ctypes.data, rows.ctypes.data, cap, buf, vlen))
+                if rc > cap:  # (fewer rows than domains: the size needed came back)
+                    cap = rc
+                elif rc > 0 and not buf.value.endswith(b"]"):  # (the value list was cut)
+                    vlen *= 16
+                elif cells[3] not in (0, 4):
+                    return cells, np.zeros((0, SPREAD_ROW_CELLS), dtype=np.int64), []
+                else:
+                    return cells, rows[:rc + 1].copy(), json.loads(buf.value.decode())
+        self._check(self._L.ykhost_headroom_affinity(self._h, 0, None, None))  # (an empty list: syncs and uploads the spec effects)
+        pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
+        one = np.array([p], dtype=np.int32)
+        self._pcheck(self._P.ykpred_headroom_affinity(self.engine, 1, one.ctypes.data, pre, filt, cells.ctypes.data))
+        if cells[3] not in (0, 4):
+            return cells, np.zeros((0, SPREAD_ROW_CELLS), dtype=np.int64), None
+        count = C.c_int32(0)
+        rows = np.zeros((1, SPREAD_ROW_CELLS), dtype=np.int64)
+        rc = self._P.ykpred_headroom_affinity_pod(self.engine, p, pre, filt, 0, rows.ctypes.data, C.byref(count))
+        if rc != 0 and count.value > 0:  # (the size came back)
+            rows = np.zeros((count.value + 1, SPREAD_ROW_CELLS), dtype=np.int64)
+            rc = self._P.ykpred_headroom_affinity_pod(self.engine, p, pre, filt, count.value, rows.ctypes.data, C.byref(count))
+        self._pcheck(rc)
+        return cells, rows[:count.value + 1].copy(), None
+
+    def headroom_affinity_constraint(self, pod, pre_mask=None, filt_mask=None):
+        """Where the anti-affinity rows behind an ask's (index or UID) cnt column lie in the topology histograms
+        (ykpred_headroom_affinity_constraint): np.int32[16] = status from the tables alone (bootstrap is not seen), topology key index,
+        mode, domains, number of live anti rows on the key, then the first cell of each in layout().spread_counts. No device work."""
+        p = int(pod if isinstance(pod, (int, np.integer)) else self.pod_index(pod))
+        self._check(self._L.ykhost_headroom_affinity(self._h, 0, None, None))  # (an empty list: syncs and uploads the spec effects)
+        pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
+        out = np.zeros(16, dtype=np.int32)
+        self._pcheck(self._P.ykpred_headroom_affinity_constraint(self.engine, p, pre, filt, out.ctypes.data))
+        return out
 
     def headroom_spread_constraint(self, pod, pre_mask=None, filt_mask=None):
         """Where the one live spread constraint of an ask (index or UID) lies in the topology histograms
