@@ -277,8 +277,7 @@ struct ykpred_engine {
   DevBuf d_explain;  // ykpred_explain: task specs | task pins | [tasks][YKPRED_EXPLAIN_BINS] counts
   DevBuf d_headroom;  // ykpred_headroom: [tasks][YKPRED_HEADROOM_CELLS] cells | [tasks] max replicas | task specs | task pins
   DevBuf d_groups;  // ykpred_headroom_groups: summaries | pair wants | pair tasks | task specs | task pins | coupled | node groups | one table chunk
-  DevBuf d_spread_head;  // ykpred_headroom_spread: summaries | tasks | one table chunk (rows | non-counting flags | unsupported)
-  DevBuf d_aff_head;  // ykpred_headroom_affinity: summaries | tasks | one table chunk (rows | unsupported)
+  DevBuf d_domain_head;  // headroom_domains_run (ykpred_headroom_spread, _affinity): summaries | tasks | one table chunk (rows | extra cells)
   DevBuf d_bytes_gather;  // ykpred_comm_allgather_bytes
   DevBuf d_topo_agree;  // node-sharded: the shape of every rank's topology histograms (agree_topology)
   u64 dict_digest = 0;  // ykpred_set_dictionary_digest
@@ -4555,6 +4554,13 @@ static bool headroom_coupled(const ykpred_engine* e, int32_t spec, uint32_t pre,
   return (spread_en || ipa_en) && (size_t)spec < e->spec_sig_spread.size() && e->spec_sig_spread[(size_t)spec] >= 0;
 }
 
+// What the ranks of a sharded engine must hold alike beside the ask list — the tune that shapes the chunks, the call's own arguments —
+// as one word for headroom_prepare's agreement: FNV-1a steps over the words (`h` continues a hash).
+static u64 tune_hash(std::initializer_list<u64> words, u64 h = 0x9e3779b97f4a7c15ull) {
+  for (const u64 w : words) h = (h ^ w) * 0x100000001b3ull;
+  return h;
+}
+
 // What ykpred_headroom and ykpred_headroom_groups share in front of their kernels: the argument checks, the TASKS of the list, the
 // topology histograms, and — on a node-sharded engine — the agreement all-gather.
 extern "C++" {  // (a template: the surrounding block has C linkage)
@@ -4762,12 +4768,9 @@ int32_t ykpred_headroom_groups(ykpred_engine_t* e, int32_t n_asks, const int32_t
       if (node_group[n] < -1 || node_group[n] >= G) return *why = "headroom_groups: group id of node " + std::to_string(n) + " outside [-1, num_groups)", YKPRED_E_INVALID;
     return YKPRED_OK;
   };
-  u64 more = 0x9e3779b97f4a7c15ull;
-  more = (more ^ (u64)(uint32_t)G) * 0x100000001b3ull;
-  more = (more ^ (u64)(uint32_t)e->group_scratch_mb) * 0x100000001b3ull;
-  more = (more ^ (u64)(uint32_t)e->group_chunk_tasks) * 0x100000001b3ull;
+  u64 more = tune_hash({(u64)(uint32_t)G, (u64)(uint32_t)e->group_scratch_mb, (u64)(uint32_t)e->group_chunk_tasks});
   if (n_asks > 0 && asks && out_summary)
-    for (int i = 0; i < n_asks; ++i) more = (more ^ (u64)(want ? want[i] : 1)) * 0x100000001b3ull;
+    for (int i = 0; i < n_asks; ++i) more = tune_hash({(u64)(want ? want[i] : 1)}, more);
   HeadroomTasks tasks;
   bool run = false;
   const int32_t rc = headroom_prepare(e, "headroom_groups", n_asks, asks, n_asks <= 0 || (asks && out_summary), pre, filt, more_checks, more, &tasks, &run);
@@ -4895,67 +4898,50 @@ static int spread_live_constraint(const ykpred_engine* e, int32_t spec, uint32_t
   return 0;
 }
 
-// Headroom of asks with ONE live hard spread constraint (DESIGN.md §4.14): k_headroom_spread gathers cap / nodes per domain of the
-// constraint's key, k_spread_fill derives the copies per domain and the summary from them and the resident histogram row. The table is
-// ragged — a task owns dom_size rows of its own key — and is worked through in TABLE CHUNKS under ykpred_headroom_groups' scratch budget
-// (group_scratch_mb, group_chunk_tasks); a chunk's accumulation form follows from its largest dom_size (group_lds). Both entry points run
-// this routine; `rows` (may be null) receives the [dom_size][4] rows of the FIRST task when that task came out at status 0.
+// Headroom over RAGGED DOMAIN TABLES: the one driver behind ykpred_headroom_spread and ykpred_headroom_affinity and their
+// *_pod calls. A task owns a run of [kSpreadRowCells] rows of its own topology key and V::kExtra cells beside them; the table is worked
+// through in TABLE CHUNKS under ykpred_headroom_groups' scratch budget (group_scratch_mb, group_chunk_tasks): consecutive tasks while their
+// rows fit, at least one. Scratch: summaries | tasks | one table chunk (rows | extra cells, task after task per kind). Per chunk: memset,
+// the variant's gather (LDS form when the chunk's widest task allows it and group_lds does), all-reduce on a sharded engine, the variant's
+// fill. `rows` (may be null) receives the rows of the FIRST task. The variant V says what differs (SpreadHeadroom, AffinityHeadroom):
+//   Task, kCells, kExtra        the device task struct, cells per summary, extra cells per task
+//   checks(why), hash(tune)     the call's own argument checks, and what the ranks must hold alike beside the tune
+//   begin()                     once the spread tables are current
+//   classify(spec, pin, &rows, &width)   the task with the host's verdict, the rows it owns and the width that picks the chunk's forms
+//   host_answer(task, routed, row)       the summary without a node and without shards: no kernel runs
+//   gather(...), fill(...)      the two launches of a chunk
 extern "C++" {
-static int32_t headroom_spread_run(ykpred_engine* e, const std::string& name, int32_t n_asks, const int32_t* asks, bool pointers_ok, uint32_t pre,
-                                   uint32_t filt, int64_t* out, std::vector<int64_t>* rows) {
-  static_assert(ykk::kSpreadHeadCells == YKPRED_SPREAD_HEADROOM_CELLS, "k_spread_fill writes the layout of ykpred.h");
-  constexpr size_t B = YKPRED_SPREAD_HEADROOM_CELLS, RC = ykk::kSpreadRowCells;
-  auto more_checks = [&](std::string* why) -> int {
-    if (!(filt & YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD)) return *why = name + ": PodTopologySpread must be in the Filter list (ykpred_headroom answers without it)", YKPRED_E_INVALID;
-    return YKPRED_OK;
-  };
-  u64 more = 0x9e3779b97f4a7c15ull;
-  more = (more ^ (u64)(uint32_t)e->group_scratch_mb) * 0x100000001b3ull;
-  more = (more ^ (u64)(uint32_t)e->group_chunk_tasks) * 0x100000001b3ull;
-  more = (more ^ (u64)(uint32_t)e->group_lds) * 0x100000001b3ull;
+struct HeadroomVariant {
+  ykpred_engine* e;
+  std::string name;
+  uint32_t pre, filt;
+};
+
+template <class V>
+static int32_t headroom_domains_run(V& v, int32_t n_asks, const int32_t* asks, bool pointers_ok, int64_t* out, std::vector<int64_t>* rows) {
+  using Task = typename V::Task;
+  constexpr size_t B = V::kCells, X = V::kExtra, RC = ykk::kSpreadRowCells;
+  ykpred_engine* e = v.e;
+  const u64 more = v.hash(tune_hash({(u64)(uint32_t)e->group_scratch_mb, (u64)(uint32_t)e->group_chunk_tasks, (u64)(uint32_t)e->group_lds}));
   HeadroomTasks tasks;
   bool run = false;
-  const int32_t rc = headroom_prepare(e, name, n_asks, asks, pointers_ok, pre, filt, more_checks, more, &tasks, &run);
+  const int32_t rc = headroom_prepare(e, v.name, n_asks, asks, pointers_ok, v.pre, v.filt, [&](std::string* why) { return v.checks(why); }, more, &tasks, &run);
   if (!run) return rc;
   const bool sharded = e->comm && e->comm_world > 1;
   hipStream_t st = e->own_stream;
   if (e->spread_dirty) TRY(build_spread_tables(e, st));
   const size_t T = tasks.spec.size();
-  // Which tasks qualify, from the signature tables: exactly one LIVE constraint, of kind SPREAD, and the PreFilter of the plugin ran
-  // (without it every Filter call is an error and nothing is placed: the ask stays at status 2).
-  std::vector<int32_t> sig_row0(e->spread_sig.size() + 1, 0);
-  for (size_t d = 0; d < e->spread_sig.size(); ++d) sig_row0[d + 1] = sig_row0[d] + (int32_t)e->spread_sig[d].size();
-  std::vector<ykk::SpreadHeadTask> ht(T);
-  std::vector<int64_t> t_rows(T, 0);
-  for (size_t k = 0; k < T; ++k) {
-    ykk::SpreadHeadTask& h = ht[k];
-    h = ykk::SpreadHeadTask{tasks.spec[k], tasks.pin[k], -1, -1, 0, 2, 0};
-    int32_t d = -1;
-    int at = -1;
-    h.status = spread_live_constraint(e, tasks.spec[k], pre, filt, &d, &at);
-    if (h.status != 0) continue;
-    const ykpred_spread_t& c = e->spread_sig[(size_t)d][(size_t)at];
-    h.sig = d;
-    h.g = sig_row0[(size_t)d] + at;
-    h.status = 0;
-    t_rows[k] = (size_t)c.topology_key < e->h_domain_sizes.size() ? e->h_domain_sizes[(size_t)c.topology_key] : 0;
-  }
+  v.begin();
+  std::vector<Task> ht(T);
+  std::vector<int64_t> t_rows(T, 0), t_width(T, 0);
+  for (size_t k = 0; k < T; ++k) ht[k] = v.classify(tasks.spec[k], tasks.pin[k], &t_rows[k], &t_width[k]);
   std::vector<int64_t> sums(T * B, 0);
   if (e->N == 0 && !sharded) {
-    // (no node: no histogram was built and no kernel runs; the verdicts above are the whole answer. A shard without nodes of a sharded
+    // (no node: no histogram was built and no kernel runs; the host's verdicts are the whole answer. A shard without nodes of a sharded
     // engine takes the other branch: it holds the cluster-wide histograms and joins the reduces)
     for (size_t k = 0; k < T; ++k) {
-      int64_t* row = sums.data() + k * B;
       const bool routed = (size_t)ht[k].spec < e->h_sflags.size() && (e->h_sflags[(size_t)ht[k].spec] & YKPRED_SPEC_UNSUPPORTED);
-      if (routed) ht[k].status = 1;  // (what k_spread_fill reads from the device's spec table)
-      row[3] = ht[k].status;
-      if (ht[k].status == 2) row[0] = row[2] = -1;
-      if (ht[k].status == 0) {
-        const ykpred_spread_t& c = e->spread_sig[(size_t)ht[k].sig][(size_t)(ht[k].g - sig_row0[(size_t)ht[k].sig])];
-        row[7] = row[11] = -1;
-        row[12] = c.topology_key;
-        row[13] = c.max_skew;
-      }
+      v.host_answer(ht[k], routed, sums.data() + k * B);
     }
     if (rows) rows->clear();
   } else {
@@ -4966,7 +4952,7 @@ static int32_t headroom_spread_run(ykpred_engine* e, const std::string& name, in
     {
       size_t bytes = 0, count = 0;
       for (size_t k = 0; k < T; ++k) {
-        const size_t need = ((size_t)t_rows[k] * RC + 2) * sizeof(int64_t);
+        const size_t need = ((size_t)t_rows[k] * RC + X) * sizeof(int64_t);
         const bool full = e->group_chunk_tasks > 0 ? count >= (size_t)e->group_chunk_tasks : (count > 0 && bytes + need > budget);
         if (full) {
           chunk_begin.push_back(k);
@@ -4979,43 +4965,31 @@ static int32_t headroom_spread_run(ykpred_engine* e, const std::string& name, in
       chunk_begin.push_back(T);
     }
     auto up8 = [](size_t b) { return (b + 7) & ~(size_t)7; };
-    const size_t o_tasks = T * B * sizeof(int64_t), o_table = up8(o_tasks + T * sizeof(ykk::SpreadHeadTask));
-    HIPCHK(e->d_spread_head.ensure(o_table + biggest + 64));
-    char* base = e->d_spread_head.as<char>();
+    const size_t o_tasks = T * B * sizeof(int64_t), o_table = up8(o_tasks + T * sizeof(Task));
+    HIPCHK(e->d_domain_head.ensure(o_table + biggest + 64));
+    char* base = e->d_domain_head.as<char>();
     int64_t* d_summary = (int64_t*)base;
-    ykk::SpreadHeadTask* d_tasks = (ykk::SpreadHeadTask*)(base + o_tasks);
+    Task* d_tasks = (Task*)(base + o_tasks);
     int64_t* d_table = (int64_t*)(base + o_table);
     // (row0 counts from the start of the task's chunk)
     for (size_t ci = 0; ci + 1 < chunk_begin.size(); ++ci) {
       int64_t at = 0;
       for (size_t k = chunk_begin[ci]; k < chunk_begin[ci + 1]; ++k) ht[k].row0 = at, at += t_rows[k];
     }
-    HIPCHK(hipMemcpyAsync(d_tasks, ht.data(), T * sizeof(ykk::SpreadHeadTask), hipMemcpyHostToDevice, st));
-    const ykk::AffSigs as{e->d_sig_aff_flags.as<unsigned>(), e->d_sig_aff_off.as<int>(), e->d_sig_aff_terms.as<u64>(), e->d_sig_pre_off.as<int>(),
-                          e->d_sig_pre_terms.as<u64>()};
-    const uint32_t filt_fit = filt & ~(uint32_t)YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD;
+    HIPCHK(hipMemcpyAsync(d_tasks, ht.data(), T * sizeof(Task), hipMemcpyHostToDevice, st));
     for (size_t ci = 0; ci + 1 < chunk_begin.size(); ++ci) {
       const size_t c0 = chunk_begin[ci], tc = chunk_begin[ci + 1] - c0;
       size_t n_rows = 0;
       int64_t widest = 0;
-      for (size_t k = c0; k < c0 + tc; ++k) n_rows += (size_t)t_rows[k], widest = std::max(widest, t_rows[k]);
-      int64_t* d_flags = d_table + n_rows * RC;
-      int64_t* d_unsupported = d_flags + tc;
-      const size_t cells = n_rows * RC + 2 * tc;
+      for (size_t k = c0; k < c0 + tc; ++k) n_rows += (size_t)t_rows[k], widest = std::max(widest, t_width[k]);
+      int64_t* d_extra = d_table + n_rows * RC;
+      const size_t cells = n_rows * RC + X * tc;
       HIPCHK(hipMemsetAsync(d_table, 0, cells * sizeof(int64_t), st));
       const dim3 grid((unsigned)((tc + ykk::kExplainTasks - 1) / ykk::kExplainTasks), (unsigned)(((size_t)e->N + ykk::kBlock - 1) / ykk::kBlock));
-      if (e->N == 0) {
-      } else if (widest <= ykk::kGroupLdsMaxGroups && e->group_lds != 0)
-        hipLaunchKernelGGL(ykk::k_headroom_spread<true>, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e), as, e->d_sig_tol.as<u64>(),
-                           (int)tc, d_tasks + c0, pre, filt_fit, (ykk::i64*)d_table, (ykk::i64*)d_flags, (ykk::i64*)d_unsupported);
-      else
-        hipLaunchKernelGGL(ykk::k_headroom_spread<false>, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e), as, e->d_sig_tol.as<u64>(),
-                           (int)tc, d_tasks + c0, pre, filt_fit, (ykk::i64*)d_table, (ykk::i64*)d_flags, (ykk::i64*)d_unsupported);
+      if (e->N > 0) v.gather(widest <= ykk::kGroupLdsMaxGroups && e->group_lds != 0, grid, tc, d_tasks + c0, d_table, d_extra, st);
       HIPCHK(hipGetLastError());
       if (sharded) NCCLCHK(rccl()->AllReduce(d_table, d_table, cells, ncclInt64, ncclSum, e->comm, st));
-      hipLaunchKernelGGL(ykk::k_spread_fill, dim3((unsigned)((tc + ykk::kWavesPerBlock - 1) / ykk::kWavesPerBlock)), dim3(ykk::kBlock), 0, st, (int)tc,
-                         d_tasks + c0, spread_sigs(e), (ykk::i64*)d_table, (const ykk::i64*)d_flags, (const ykk::i64*)d_unsupported,
-                         (ykk::i64*)(d_summary + c0 * B));
+      v.fill(tc, widest, d_tasks + c0, d_table, d_extra, d_summary + c0 * B, st);
       HIPCHK(hipGetLastError());
       if (rows && ci == 0) {
         rows->assign((size_t)t_rows[0] * RC, 0);
@@ -5029,6 +5003,99 @@ static int32_t headroom_spread_run(ykpred_engine* e, const std::string& name, in
   for (int i = 0; i < n_asks; ++i) memcpy(out + (size_t)i * B, sums.data() + (size_t)tasks.task_of[(size_t)i] * B, B * sizeof(int64_t));
   return YKPRED_OK;
 }
+
+// The per-domain rows behind ONE ask's summary (the *_pod calls; v.name ends in "_pod"). On a sharded engine the whole computation is the
+// collective one of the list call; the argument checks that only this rank can fail come after it. A variant with an outside row
+// (V::kOutsideRow) always writes it, behind the domains.
+template <class V>
+static int32_t headroom_domains_pod(V& v, int32_t pod, int32_t max_domains, int64_t* out, int32_t* num_domains) {
+  constexpr size_t RC = ykk::kSpreadRowCells, outside = V::kOutsideRow ? 1 : 0;
+  ykpred_engine* e = v.e;
+  int64_t cells[V::kCells];
+  std::vector<int64_t> rows;
+  const int32_t rc = headroom_domains_run(v, 1, &pod, num_domains != nullptr && max_domains >= 0 && (out || (max_domains == 0 && !outside)), cells, &rows);
+  if (rc != YKPRED_OK) return rc;
+  if (!V::has_rows(cells[3]))
+    return fail(e, YKPRED_E_UNSUPPORTED, v.name + ": the ask is at status " + std::to_string((long long)cells[3]) + " (ykpred_" + v.name.substr(0, v.name.size() - 4) + "): it has no per-domain rows");
+  const size_t D = rows.empty() ? 0 : rows.size() / RC - outside;
+  *num_domains = (int32_t)D;
+  if ((size_t)max_domains < D) return fail(e, YKPRED_E_INVALID, v.name + ": out holds fewer than " + std::to_string(D) + " domains" + (outside ? " and the outside row" : ""));
+  std::fill(out, out + (D + outside) * RC, (int64_t)0);  // (no node: no table, every row 0)
+  if (!rows.empty()) memcpy(out, rows.data(), rows.size() * sizeof(int64_t));
+  return YKPRED_OK;
+}
+}  // extern "C++"
+
+// What the two *_constraint calls check first → the ask's spec. `lists_ok`: the plugin lists carry what the call needs.
+static int32_t headroom_constraint_spec(ykpred_engine* e, const std::string& name, int32_t pod, const int32_t* out, bool lists_ok, const char* lists_text,
+                                        int32_t* spec) {
+  if (!e || !out) return fail(e, YKPRED_E_INVALID, name + ": bad argument");
+  if (!e->nodes_set || !e->specs_set || !e->pods_set) return fail(e, YKPRED_E_STATE, name + ": tables not uploaded");
+  if (pod < 0 || pod >= e->P) return fail(e, YKPRED_E_INVALID, name + ": index out of range");
+  if (!lists_ok) return fail(e, YKPRED_E_INVALID, name + ": " + lists_text);
+  *spec = e->h_pod_spec[(size_t)pod];
+  return YKPRED_OK;
+}
+
+// Headroom of asks with ONE live hard spread constraint (DESIGN.md §4.14): k_headroom_spread gathers cap / nodes per domain of the
+// constraint's key, k_spread_fill derives the copies per domain and the summary from them and the resident histogram row. A task owns
+// dom_size rows; beside them a non-counting flag and `unsupported`. `rows` of the driver: [dom_size][4] when the first task is at status 0.
+extern "C++" {
+struct SpreadHeadroom : HeadroomVariant {
+  using Task = ykk::SpreadHeadTask;
+  static_assert(ykk::kSpreadHeadCells == YKPRED_SPREAD_HEADROOM_CELLS, "k_spread_fill writes the layout of ykpred.h");
+  static constexpr size_t kCells = YKPRED_SPREAD_HEADROOM_CELLS, kExtra = 2;
+  static constexpr bool kOutsideRow = false;
+  static bool has_rows(int64_t status) { return status == 0; }
+  std::vector<int32_t> sig_row0;  // first row of a signature in SpreadSigs.c
+
+  int checks(std::string* why) const {
+    if (!(filt & YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD)) return *why = name + ": PodTopologySpread must be in the Filter list (ykpred_headroom answers without it)", YKPRED_E_INVALID;
+    return YKPRED_OK;
+  }
+  u64 hash(u64 tune) const { return tune; }
+  void begin() {
+    sig_row0.assign(e->spread_sig.size() + 1, 0);
+    for (size_t d = 0; d < e->spread_sig.size(); ++d) sig_row0[d + 1] = sig_row0[d] + (int32_t)e->spread_sig[d].size();
+  }
+  // Which tasks qualify, from the signature tables: exactly one LIVE constraint, of kind SPREAD, and the PreFilter of the plugin ran
+  // (without it every Filter call is an error and nothing is placed: the ask stays at status 2).
+  Task classify(int32_t spec, int32_t pin, int64_t* n_rows, int64_t* width) const {
+    Task h{spec, pin, -1, -1, 0, 2, 0};
+    int32_t d = -1;
+    int at = -1;
+    h.status = spread_live_constraint(e, spec, pre, filt, &d, &at);
+    if (h.status != 0) return h;
+    const ykpred_spread_t& c = e->spread_sig[(size_t)d][(size_t)at];
+    h.sig = d;
+    h.g = sig_row0[(size_t)d] + at;
+    *n_rows = *width = (size_t)c.topology_key < e->h_domain_sizes.size() ? e->h_domain_sizes[(size_t)c.topology_key] : 0;
+    return h;
+  }
+  void host_answer(const Task& h, bool routed, int64_t* row) const {
+    const int status = routed ? 1 : h.status;  // (routed: what k_spread_fill reads from the device's spec table)
+    row[3] = status;
+    if (status == 2) row[0] = row[2] = -1;
+    if (status == 0) {
+      const ykpred_spread_t& c = e->spread_sig[(size_t)h.sig][(size_t)(h.g - sig_row0[(size_t)h.sig])];
+      row[7] = row[11] = -1;
+      row[12] = c.topology_key;
+      row[13] = c.max_skew;
+    }
+  }
+  // (replicas runs under the Filter list WITHOUT the spread bit; the extra cells: tc non-counting flags, then tc unsupported)
+  void gather(bool lds, dim3 grid, size_t tc, const Task* d_tasks, int64_t* d_table, int64_t* d_extra, hipStream_t st) const {
+    const ykk::AffSigs as{e->d_sig_aff_flags.as<unsigned>(), e->d_sig_aff_off.as<int>(), e->d_sig_aff_terms.as<u64>(), e->d_sig_pre_off.as<int>(),
+                          e->d_sig_pre_terms.as<u64>()};
+    hipLaunchKernelGGL(lds ? ykk::k_headroom_spread<true> : ykk::k_headroom_spread<false>, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e), as,
+                       e->d_sig_tol.as<u64>(), (int)tc, d_tasks, pre, filt & ~(uint32_t)YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD, (ykk::i64*)d_table,
+                       (ykk::i64*)d_extra, (ykk::i64*)(d_extra + tc));
+  }
+  void fill(size_t tc, int64_t widest, const Task* d_tasks, int64_t* d_table, int64_t* d_extra, int64_t* d_summary, hipStream_t st) const {
+    hipLaunchKernelGGL(ykk::k_spread_fill, dim3((unsigned)((tc + ykk::kWavesPerBlock - 1) / ykk::kWavesPerBlock)), dim3(ykk::kBlock), 0, st, (int)tc,
+                       d_tasks, spread_sigs(e), (ykk::i64*)d_table, (const ykk::i64*)d_extra, (const ykk::i64*)(d_extra + tc), (ykk::i64*)d_summary);
+  }
+};
 }  // extern "C++"
 
 int32_t ykpred_headroom_spread(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, uint32_t pre, uint32_t filt, int64_t* out) {
@@ -5036,41 +5103,28 @@ int32_t ykpred_headroom_spread(ykpred_engine_t* e, int32_t n_asks, const int32_t
   Range roctx_range("ykpred:headroom_spread");
   if (e) e->n_queries++;
   if (!e) return YKPRED_E_INVALID;
-  return headroom_spread_run(e, "headroom_spread", n_asks, asks, n_asks <= 0 || (asks && out), pre, filt, out, nullptr);
+  SpreadHeadroom v{{e, "headroom_spread", pre, filt}, {}};
+  return headroom_domains_run(v, n_asks, asks, n_asks <= 0 || (asks && out), out, nullptr);
 }
 
-// The per-domain rows behind one ask's summary. On a sharded engine the whole computation is the collective one of ykpred_headroom_spread;
-// the argument checks that only this rank can fail come after it.
 int32_t ykpred_headroom_spread_pod(ykpred_engine_t* e, int32_t pod, uint32_t pre, uint32_t filt, int32_t max_domains, int64_t* out,
                                    int32_t* num_domains) {
   YK_SERIALISE(e);
   Range roctx_range("ykpred:headroom_spread_pod");
   if (e) e->n_queries++;
   if (!e) return YKPRED_E_INVALID;
-  int64_t cells[YKPRED_SPREAD_HEADROOM_CELLS];
-  std::vector<int64_t> rows;
-  const int32_t rc = headroom_spread_run(e, "headroom_spread_pod", 1, &pod, num_domains != nullptr && max_domains >= 0 && (out || max_domains == 0), pre,
-                                         filt, cells, &rows);
-  if (rc != YKPRED_OK) return rc;
-  if (cells[3] != 0)
-    return fail(e, YKPRED_E_UNSUPPORTED, "headroom_spread_pod: the ask is at status " + std::to_string((long long)cells[3]) + " (ykpred_headroom_spread): it has no per-domain rows");
-  const size_t D = rows.size() / ykk::kSpreadRowCells;
-  *num_domains = (int32_t)D;
-  if ((size_t)max_domains < D) return fail(e, YKPRED_E_INVALID, "headroom_spread_pod: out holds fewer than " + std::to_string(D) + " domains");
-  if (D) memcpy(out, rows.data(), rows.size() * sizeof(int64_t));
-  return YKPRED_OK;
+  SpreadHeadroom v{{e, "headroom_spread_pod", pre, filt}, {}};
+  return headroom_domains_pod(v, pod, max_domains, out, num_domains);
 }
 
 // Where the one live spread constraint of an ask lives in the topology histograms (layout.spread_counts / spread_present): what a host
 // needs to read the row ykpred_headroom_spread fills from. Tables only; no launch, nothing exchanged.
 int32_t ykpred_headroom_spread_constraint(ykpred_engine_t* e, int32_t pod, uint32_t pre, uint32_t filt, int32_t* out) {
   YK_SERIALISE(e);
-  if (!e || !out) return fail(e, YKPRED_E_INVALID, "headroom_spread_constraint: bad argument");
-  if (!e->nodes_set || !e->specs_set || !e->pods_set) return fail(e, YKPRED_E_STATE, "headroom_spread_constraint: tables not uploaded");
-  if (pod < 0 || pod >= e->P) return fail(e, YKPRED_E_INVALID, "headroom_spread_constraint: index out of range");
-  if (!(filt & YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD)) return fail(e, YKPRED_E_INVALID, "headroom_spread_constraint: PodTopologySpread must be in the Filter list");
+  int32_t spec = -1;
+  TRY(headroom_constraint_spec(e, "headroom_spread_constraint", pod, out, filt & YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD,
+                               "PodTopologySpread must be in the Filter list", &spec));
   std::fill(out, out + YKPRED_SPREAD_CONSTRAINT_CELLS, (int32_t)0);
-  const int32_t spec = e->h_pod_spec[(size_t)pod];
   int32_t d = -1;
   int at = -1;
   out[0] = spread_live_constraint(e, spec, pre, filt, &d, &at);
@@ -5135,150 +5189,75 @@ static int affinity_live_rows(const ykpred_engine* e, int32_t spec, uint32_t fil
 }
 
 // Headroom of asks whose live topology constraints are InterPodAffinity's: k_headroom_affinity gathers cap / nodes per
-// domain of the task's key and in its outside row, k_affinity_fill decides bootstrap, derives the copies per domain and the summary. The
-// table is ragged — a task owns dom_size + 1 rows — and is worked through in TABLE CHUNKS under ykpred_headroom_groups' scratch budget;
-// a chunk's accumulation form follows from its largest dom_size. Both entry points run this routine; `rows` (may be null) receives the
-// [dom_size + 1][4] rows of the FIRST task when that task came out at status 0 or 4.
+// domain of the task's key and in its outside row, k_affinity_fill decides bootstrap, derives the copies per domain and the summary. A
+// task owns dom_size + 1 rows; beside them `unsupported`. `rows` of the driver: [dom_size + 1][4] when the first task is at status 0 or 4.
 extern "C++" {
-static int32_t headroom_affinity_run(ykpred_engine* e, const std::string& name, int32_t n_asks, const int32_t* asks, bool pointers_ok, uint32_t pre,
-                                     uint32_t filt, int64_t* out, std::vector<int64_t>* rows) {
+struct AffinityHeadroom : HeadroomVariant {
+  using Task = ykk::AffHeadTask;
   static_assert(ykk::kAffHeadCells == YKPRED_AFFINITY_HEADROOM_CELLS, "k_affinity_fill writes the layout of ykpred.h");
-  constexpr size_t B = YKPRED_AFFINITY_HEADROOM_CELLS, RC = ykk::kSpreadRowCells;
-  constexpr int64_t kAffFillWideFrom = 4 * ykk::kWave;  // domains from which a task's fill gets the workgroup
-  auto more_checks = [&](std::string* why) -> int {
+  static constexpr size_t kCells = YKPRED_AFFINITY_HEADROOM_CELLS, kExtra = 1;
+  static constexpr bool kOutsideRow = true;
+  static bool has_rows(int64_t status) { return status == 0 || status == 4; }
+  static constexpr int64_t kAffFillWideFrom = 4 * ykk::kWave;  // domains from which a task's fill gets the workgroup
+
+  int checks(std::string* why) const {
     if (!(pre & filt & YKPRED_PLUGIN_INTER_POD_AFFINITY))
       return *why = name + ": InterPodAffinity must be in both plugin lists (ykpred_headroom or ykpred_headroom_spread answers without it)", YKPRED_E_INVALID;
     if (e->fx_version != e->specs_version)
       return *why = name + ": the specs' effects are not uploaded for the current spec table (ykpred_set_spec_effects): what a copy adds to the histograms is unknown", YKPRED_E_UNSUPPORTED;
     return YKPRED_OK;
-  };
-  u64 more = 0x9e3779b97f4a7c15ull;
-  more = (more ^ (u64)(uint32_t)e->group_scratch_mb) * 0x100000001b3ull;
-  more = (more ^ (u64)(uint32_t)e->group_chunk_tasks) * 0x100000001b3ull;
-  more = (more ^ (u64)(uint32_t)e->group_lds) * 0x100000001b3ull;
-  more = (more ^ (u64)(uint32_t)e->affinity_fill_waves) * 0x100000001b3ull;
-  more = (more ^ (u64)(e->fx_version == e->specs_version ? e->fx_version : 0)) * 0x100000001b3ull;  // (the effects every rank fills by)
-  HeadroomTasks tasks;
-  bool run = false;
-  const int32_t rc = headroom_prepare(e, name, n_asks, asks, pointers_ok, pre, filt, more_checks, more, &tasks, &run);
-  if (!run) return rc;
-  const bool sharded = e->comm && e->comm_world > 1;
-  hipStream_t st = e->own_stream;
-  if (e->spread_dirty) TRY(build_spread_tables(e, st));
-  const size_t T = tasks.spec.size();
-  std::vector<ykk::AffHeadTask> ht(T);
-  std::vector<int64_t> t_rows(T, 0);  // table rows of the task: its domains and the outside row, none when it does not qualify
-  for (size_t k = 0; k < T; ++k) {
-    ykk::AffHeadTask& h = ht[k];
-    h = ykk::AffHeadTask{tasks.spec[k], tasks.pin[k], -1, -1, 0, 0, 2, 0u, 0};
+  }
+  u64 hash(u64 tune) const {  // (the fill width, and the effects every rank fills by)
+    return tune_hash({(u64)(uint32_t)e->affinity_fill_waves, (u64)(e->fx_version == e->specs_version ? e->fx_version : 0)}, tune);
+  }
+  void begin() {}
+  // (the width is dom_size: the outside row has its own LDS row)
+  Task classify(int32_t spec, int32_t pin, int64_t* n_rows, int64_t* width) const {
+    Task h{spec, pin, -1, -1, 0, 0, 2, 0u, 0};
     int32_t d = -1, key = -1, mode = 0;
     uint32_t wmask = 0;
-    h.status = affinity_live_rows(e, tasks.spec[k], filt, &d, &key, &mode, &wmask);
-    if (h.status != 0) continue;
+    h.status = affinity_live_rows(e, spec, filt, &d, &key, &mode, &wmask);
+    if (h.status != 0) return h;
     h.sig = d, h.kd = key, h.mode = mode, h.wmask = wmask;
     h.dom_size = (size_t)key < e->h_domain_sizes.size() ? e->h_domain_sizes[(size_t)key] : 0;
-    t_rows[k] = (int64_t)h.dom_size + 1;
+    *width = h.dom_size;
+    *n_rows = (int64_t)h.dom_size + 1;
+    return h;
   }
-  std::vector<int64_t> sums(T * B, 0);
-  if (e->N == 0 && !sharded) {
-    // (no node: no histogram was built and no kernel runs. No pod matches anywhere, so a self-matching, self-contributing affinity row
-    // is in bootstrap: the fill's rule on the host. A shard without nodes of a sharded engine takes the other branch)
-    for (size_t k = 0; k < T; ++k) {
-      int64_t* row = sums.data() + k * B;
-      const bool routed = (size_t)ht[k].spec < e->h_sflags.size() && (e->h_sflags[(size_t)ht[k].spec] & YKPRED_SPEC_UNSUPPORTED);
-      int status = routed ? 1 : ht[k].status, mode = ht[k].mode;
-      if (status == 0) {
-        const std::vector<ykpred_spread_t>& sr = e->spread_sig[(size_t)ht[k].sig];
-        int n_aff = 0;
-        bool candidate = false;
-        for (size_t j = 0; j < sr.size(); ++j)
-          if (sr[j].kind == ykk::kKindPodAffinity) ++n_aff, candidate = candidate || (sr[j].self_match != 0 && j < 32 && ((ht[k].wmask >> j) & 1u));
-        if (candidate) {
-          if (n_aff == 1 && mode == 0) status = 4, mode = 2;
-          else status = 2;
-        }
-      }
-      row[3] = status;
-      if (status == 2) row[0] = row[2] = -1;
-      if (status == 0 || status == 4) {
-        if (status == 4) row[0] = -1;
-        row[11] = -1;
-        row[12] = ht[k].kd;
-        row[13] = mode;
+  // (no pod matches anywhere, so a self-matching, self-contributing affinity row is in bootstrap: the fill's rule on the host)
+  void host_answer(const Task& h, bool routed, int64_t* row) const {
+    int status = routed ? 1 : h.status, mode = h.mode;
+    if (status == 0) {
+      const std::vector<ykpred_spread_t>& sr = e->spread_sig[(size_t)h.sig];
+      int n_aff = 0;
+      bool candidate = false;
+      for (size_t j = 0; j < sr.size(); ++j)
+        if (sr[j].kind == ykk::kKindPodAffinity) ++n_aff, candidate = candidate || (sr[j].self_match != 0 && j < 32 && ((h.wmask >> j) & 1u));
+      if (candidate) {
+        if (n_aff == 1 && mode == 0) status = 4, mode = 2;
+        else status = 2;
       }
     }
-    if (rows) rows->clear();
-  } else {
-    // Table chunks: consecutive tasks while their rows fit the budget (at least one task; group_chunk_tasks overrides the count).
-    const size_t budget = (size_t)e->group_scratch_mb << 20;
-    std::vector<size_t> chunk_begin{0};
-    size_t biggest = 0;
-    {
-      size_t bytes = 0, count = 0;
-      for (size_t k = 0; k < T; ++k) {
-        const size_t need = ((size_t)t_rows[k] * RC + 1) * sizeof(int64_t);
-        const bool full = e->group_chunk_tasks > 0 ? count >= (size_t)e->group_chunk_tasks : (count > 0 && bytes + need > budget);
-        if (full) {
-          chunk_begin.push_back(k);
-          bytes = 0, count = 0;
-        }
-        bytes += need;
-        ++count;
-        biggest = std::max(biggest, bytes);
-      }
-      chunk_begin.push_back(T);
+    row[3] = status;
+    if (status == 2) row[0] = row[2] = -1;
+    if (status == 0 || status == 4) {
+      if (status == 4) row[0] = -1;
+      row[11] = -1;
+      row[12] = h.kd;
+      row[13] = mode;
     }
-    auto up8 = [](size_t b) { return (b + 7) & ~(size_t)7; };
-    const size_t o_tasks = T * B * sizeof(int64_t), o_table = up8(o_tasks + T * sizeof(ykk::AffHeadTask));
-    HIPCHK(e->d_aff_head.ensure(o_table + biggest + 64));
-    char* base = e->d_aff_head.as<char>();
-    int64_t* d_summary = (int64_t*)base;
-    ykk::AffHeadTask* d_tasks = (ykk::AffHeadTask*)(base + o_tasks);
-    int64_t* d_table = (int64_t*)(base + o_table);
-    // (row0 counts from the start of the task's chunk)
-    for (size_t ci = 0; ci + 1 < chunk_begin.size(); ++ci) {
-      int64_t at = 0;
-      for (size_t k = chunk_begin[ci]; k < chunk_begin[ci + 1]; ++k) ht[k].row0 = at, at += t_rows[k];
-    }
-    HIPCHK(hipMemcpyAsync(d_tasks, ht.data(), T * sizeof(ykk::AffHeadTask), hipMemcpyHostToDevice, st));
-    for (size_t ci = 0; ci + 1 < chunk_begin.size(); ++ci) {
-      const size_t c0 = chunk_begin[ci], tc = chunk_begin[ci + 1] - c0;
-      size_t n_rows = 0;
-      int64_t widest = 0;
-      for (size_t k = c0; k < c0 + tc; ++k) n_rows += (size_t)t_rows[k], widest = std::max(widest, (int64_t)ht[k].dom_size);
-      int64_t* d_unsupported = d_table + n_rows * RC;
-      const size_t cells = n_rows * RC + tc;
-      HIPCHK(hipMemsetAsync(d_table, 0, cells * sizeof(int64_t), st));
-      const dim3 grid((unsigned)((tc + ykk::kExplainTasks - 1) / ykk::kExplainTasks), (unsigned)(((size_t)e->N + ykk::kBlock - 1) / ykk::kBlock));
-      if (e->N == 0) {
-      } else if (widest <= ykk::kGroupLdsMaxGroups && e->group_lds != 0)
-        hipLaunchKernelGGL(ykk::k_headroom_affinity<true>, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e), (int)tc, d_tasks + c0, pre, filt,
-                           (ykk::i64*)d_table, (ykk::i64*)d_unsupported);
-      else
-        hipLaunchKernelGGL(ykk::k_headroom_affinity<false>, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e), (int)tc, d_tasks + c0, pre, filt,
-                           (ykk::i64*)d_table, (ykk::i64*)d_unsupported);
-      HIPCHK(hipGetLastError());
-      if (sharded) NCCLCHK(rccl()->AllReduce(d_table, d_table, cells, ncclInt64, ncclSum, e->comm, st));
-      const bool wide = e->affinity_fill_waves > 0 ? e->affinity_fill_waves > 1 : widest >= kAffFillWideFrom;
-      if (wide)
-        hipLaunchKernelGGL(ykk::k_affinity_fill<ykk::kWavesPerBlock>, dim3((unsigned)tc), dim3(ykk::kBlock), 0, st, (int)tc, d_tasks + c0, spread_sigs(e),
-                           (ykk::i64*)d_table, (const ykk::i64*)d_unsupported, (ykk::i64*)(d_summary + c0 * B));
-      else
-        hipLaunchKernelGGL(ykk::k_affinity_fill<1>, dim3((unsigned)((tc + ykk::kWavesPerBlock - 1) / ykk::kWavesPerBlock)), dim3(ykk::kBlock), 0, st, (int)tc,
-                           d_tasks + c0, spread_sigs(e), (ykk::i64*)d_table, (const ykk::i64*)d_unsupported, (ykk::i64*)(d_summary + c0 * B));
-      HIPCHK(hipGetLastError());
-      if (rows && ci == 0) {
-        rows->assign((size_t)t_rows[0] * RC, 0);
-        if (!rows->empty()) HIPCHK(hipMemcpyAsync(rows->data(), d_table, rows->size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-      }
-      // (the next chunk reuses the table: the stream orders its fill behind this chunk's kernels and copy)
-    }
-    HIPCHK(hipMemcpyAsync(sums.data(), d_summary, T * B * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
   }
-  for (int i = 0; i < n_asks; ++i) memcpy(out + (size_t)i * B, sums.data() + (size_t)tasks.task_of[(size_t)i] * B, B * sizeof(int64_t));
-  return YKPRED_OK;
-}
+  void gather(bool lds, dim3 grid, size_t tc, const Task* d_tasks, int64_t* d_table, int64_t* d_extra, hipStream_t st) const {
+    hipLaunchKernelGGL(lds ? ykk::k_headroom_affinity<true> : ykk::k_headroom_affinity<false>, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e),
+                       (int)tc, d_tasks, pre, filt, (ykk::i64*)d_table, (ykk::i64*)d_extra);
+  }
+  void fill(size_t tc, int64_t widest, const Task* d_tasks, int64_t* d_table, int64_t* d_extra, int64_t* d_summary, hipStream_t st) const {
+    const bool wide = e->affinity_fill_waves > 0 ? e->affinity_fill_waves > 1 : widest >= kAffFillWideFrom;
+    const unsigned blocks = wide ? (unsigned)tc : (unsigned)((tc + ykk::kWavesPerBlock - 1) / ykk::kWavesPerBlock);
+    hipLaunchKernelGGL(wide ? ykk::k_affinity_fill<ykk::kWavesPerBlock> : ykk::k_affinity_fill<1>, dim3(blocks), dim3(ykk::kBlock), 0, st, (int)tc, d_tasks,
+                       spread_sigs(e), (ykk::i64*)d_table, (const ykk::i64*)d_extra, (ykk::i64*)d_summary);
+  }
+};
 }  // extern "C++"
 
 int32_t ykpred_headroom_affinity(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, uint32_t pre, uint32_t filt, int64_t* out) {
@@ -5286,43 +5265,30 @@ int32_t ykpred_headroom_affinity(ykpred_engine_t* e, int32_t n_asks, const int32
   Range roctx_range("ykpred:headroom_affinity");
   if (e) e->n_queries++;
   if (!e) return YKPRED_E_INVALID;
-  return headroom_affinity_run(e, "headroom_affinity", n_asks, asks, n_asks <= 0 || (asks && out), pre, filt, out, nullptr);
+  AffinityHeadroom v{{e, "headroom_affinity", pre, filt}};
+  return headroom_domains_run(v, n_asks, asks, n_asks <= 0 || (asks && out), out, nullptr);
 }
 
-// The per-domain rows behind one ask's summary, the outside row last. On a sharded engine the whole computation is the collective one of
-// ykpred_headroom_affinity; the argument checks that only this rank can fail come after it.
+// (the outside row last)
 int32_t ykpred_headroom_affinity_pod(ykpred_engine_t* e, int32_t pod, uint32_t pre, uint32_t filt, int32_t max_domains, int64_t* out,
                                      int32_t* num_domains) {
   YK_SERIALISE(e);
   Range roctx_range("ykpred:headroom_affinity_pod");
   if (e) e->n_queries++;
   if (!e) return YKPRED_E_INVALID;
-  int64_t cells[YKPRED_AFFINITY_HEADROOM_CELLS];
-  std::vector<int64_t> rows;
-  const int32_t rc = headroom_affinity_run(e, "headroom_affinity_pod", 1, &pod, num_domains != nullptr && max_domains >= 0 && out != nullptr, pre, filt,
-                                           cells, &rows);
-  if (rc != YKPRED_OK) return rc;
-  if (cells[3] != 0 && cells[3] != 4)
-    return fail(e, YKPRED_E_UNSUPPORTED, "headroom_affinity_pod: the ask is at status " + std::to_string((long long)cells[3]) + " (ykpred_headroom_affinity): it has no per-domain rows");
-  const size_t D = rows.empty() ? 0 : rows.size() / ykk::kSpreadRowCells - 1;
-  *num_domains = (int32_t)D;
-  if ((size_t)max_domains < D) return fail(e, YKPRED_E_INVALID, "headroom_affinity_pod: out holds fewer than " + std::to_string(D) + " domains and the outside row");
-  std::fill(out, out + (D + 1) * ykk::kSpreadRowCells, (int64_t)0);  // (no node: no table, every row 0)
-  if (!rows.empty()) memcpy(out, rows.data(), rows.size() * sizeof(int64_t));
-  return YKPRED_OK;
+  AffinityHeadroom v{{e, "headroom_affinity_pod", pre, filt}};
+  return headroom_domains_pod(v, pod, max_domains, out, num_domains);
 }
 
 // Where the live anti rows on an ask's key lie in the topology histograms (layout.spread_counts): what a host needs to read the cells
 // ykpred_headroom_affinity sums into cnt. Tables and effects only; no launch, nothing exchanged.
 int32_t ykpred_headroom_affinity_constraint(ykpred_engine_t* e, int32_t pod, uint32_t pre, uint32_t filt, int32_t* out) {
   YK_SERIALISE(e);
-  if (!e || !out) return fail(e, YKPRED_E_INVALID, "headroom_affinity_constraint: bad argument");
-  if (!e->nodes_set || !e->specs_set || !e->pods_set) return fail(e, YKPRED_E_STATE, "headroom_affinity_constraint: tables not uploaded");
-  if (pod < 0 || pod >= e->P) return fail(e, YKPRED_E_INVALID, "headroom_affinity_constraint: index out of range");
-  if (!(pre & filt & YKPRED_PLUGIN_INTER_POD_AFFINITY)) return fail(e, YKPRED_E_INVALID, "headroom_affinity_constraint: InterPodAffinity must be in both plugin lists");
+  int32_t spec = -1;
+  TRY(headroom_constraint_spec(e, "headroom_affinity_constraint", pod, out, pre & filt & YKPRED_PLUGIN_INTER_POD_AFFINITY,
+                               "InterPodAffinity must be in both plugin lists", &spec));
   if (e->fx_version != e->specs_version) return fail(e, YKPRED_E_UNSUPPORTED, "headroom_affinity_constraint: the specs' effects are not uploaded for the current spec table (ykpred_set_spec_effects)");
   std::fill(out, out + YKPRED_AFFINITY_CONSTRAINT_CELLS, (int32_t)0);
-  const int32_t spec = e->h_pod_spec[(size_t)pod];
   int32_t d = -1, key = -1, mode = 0;
   uint32_t wmask = 0;
   out[0] = affinity_live_rows(e, spec, filt, &d, &key, &mode, &wmask);

@@ -2981,12 +2981,49 @@ __device__ __forceinline__ int replicas(const SpecTable& s, int spec, int pin, i
   return (int)max((i64)1, k);  // (k >= 1 by the fit: NodeResourcesFit is in both lists, the host checked)
 }
 
-// Grid and walk of k_explain: blockIdx.x = chunk of kExplainTasks tasks, blockIdx.y = group of 4 node words, lane = node, the wave walks
-// the chunk's tasks. Per task and wave: Σ replicas by a wave reduction (at most 64 x 2^31 = 2^37), the node counts by ballot popcounts
-// (lane c keeps cell c), max replicas by a wave max. The block's waves meet in LDS; the block then issues one global integer add per
-// non-zero cell of cells[tasks][16] and one integer max per non-zero entry of maxk[tasks], both zeroed on the stream by the host. No
-// float anywhere: the result does not depend on the order of arrival. Cell [3] is written by the first node group alone: 1 for a spec
-// the engine does not evaluate (every other cell of such a task stays 0: eval_pair rejects every pair).
+// THE GATHER WALK of k_headroom, k_headroom_groups, k_headroom_spread and k_headroom_affinity (grid of k_explain): blockIdx.x = chunk of
+// kExplainTasks tasks [k0, kend), blockIdx.y = 256 nodes, lane = node. The node columns are loaded once per chunk; the task data is
+// wave-uniform. Per task: task(k, &spec, &pin) names the pair or returns false to skip the task (wave-uniform); a task on which no lane
+// of the wave takes a copy is skipped; then body(k, rep, binder, fits, nr, n) runs — on the lanes with rep > 0, or, with EVERY_LANE, on
+// the whole wave (a body that ballots and shuffles; fits = the ballot of rep > 0). A wave wholly past N skips the walk, not the caller's
+// barriers. Everything a gather adds is an integer add: no result depends on the order of arrival.
+__device__ __forceinline__ int headroom_node(const NodeTable& t, bool* live) {
+  const int n = (blockIdx.y * kWavesPerBlock + threadIdx.x / kWave) * kWave + threadIdx.x % kWave;
+  *live = n < t.n;
+  return *live ? n : -1;
+}
+template <bool EVERY_LANE, class Task, class Body>
+__device__ __forceinline__ void headroom_walk(const NodeTable& t, const SpecTable& s, int k0, int kend, unsigned pre_mask, unsigned filt_mask, Task task,
+                                              Body body) {
+  bool live;
+  const int n = headroom_node(t, &live);
+  if (!__ballot(live)) return;  // (wave-uniform)
+  NodeRegs nr;
+  load_node(t, n, &nr);
+  const i64 slots = live ? (i64)t.allowed[n] - (i64)t.count[n] : 0;
+  for (int k = k0; k < kend; ++k) {
+    int spec = 0, pin = 0;
+    if (!task(k, &spec, &pin)) continue;  // (wave-uniform)
+    int binder = 0;
+    const int rep = live ? replicas(s, spec, pin, n, nr, slots, pre_mask, filt_mask, &binder) : 0;
+    const u64 fits = __ballot(rep > 0);
+    if (!fits) continue;  // (wave-uniform: no lane fits)
+    if (!EVERY_LANE && rep <= 0) continue;
+    body(k, rep, binder, fits, nr, n);
+  }
+}
+// The tail of every gather: the first node group alone writes flag[k * stride] = 1 for the tasks of the chunk whose spec the engine does
+// not evaluate (every other cell of such a task stays 0: eval_pair rejects every pair).
+template <class SpecOf>
+__device__ __forceinline__ void headroom_unsupported(const SpecTable& s, int k0, int kend, SpecOf spec_of, i64* __restrict__ flag, int stride) {
+  const int k = k0 + (int)threadIdx.x;
+  if (blockIdx.y == 0 && k < kend && (s.flags[spec_of(k)] & kSpecUnsupported)) flag[(size_t)k * stride] = 1;
+}
+
+// k_headroom, per task and wave: Σ replicas by a wave reduction (at most 64 x 2^31 = 2^37), the node counts by ballot popcounts (lane c
+// keeps cell c), max replicas by a wave max. The block's waves meet in LDS; the block then issues one global integer add per non-zero
+// cell of cells[tasks][16] and one integer max per non-zero entry of maxk[tasks], both zeroed on the stream by the host. Cell [3] is the
+// `unsupported` flag.
 __global__ __launch_bounds__(kBlock) void k_headroom(NodeTable t, SpecTable s, int n_tasks, const int* __restrict__ task_spec,
                                                      const int* __restrict__ task_pin, unsigned pre_mask, unsigned filt_mask,
                                                      i64* __restrict__ cells, i64* __restrict__ maxk) {
@@ -2995,45 +3032,35 @@ __global__ __launch_bounds__(kBlock) void k_headroom(NodeTable t, SpecTable s, i
   for (int i = threadIdx.x; i < kExplainTasks * kHeadroomCells; i += kBlock) acc[i] = 0;
   if (threadIdx.x < kExplainTasks) accmax[threadIdx.x] = 0;
   __syncthreads();
-  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-  int n = (blockIdx.y * kWavesPerBlock + wave) * kWave + lane;
-  const bool live = n < t.n;
-  if (!live) n = -1;
+  const int lane = threadIdx.x % kWave;
   const int k0 = blockIdx.x * kExplainTasks, kend = min(k0 + kExplainTasks, n_tasks);
-  if (__ballot(live)) {  // (wave-uniform: a wave wholly past N skips the walk, not the barriers)
-    NodeRegs nr;
-    load_node(t, n, &nr);
-    const i64 slots = live ? (i64)t.allowed[n] - (i64)t.count[n] : 0;
-    for (int k = k0; k < kend; ++k) {
-      int binder = 0;
-      const int rep = live ? replicas(s, task_spec[k], task_pin[k], n, nr, slots, pre_mask, filt_mask, &binder) : 0;
-      const u64 fits = __ballot(rep > 0);
-      if (!fits) continue;  // (wave-uniform)
-      i64 sum = rep;
-      int mx = rep;
+  headroom_walk<true>(
+      t, s, k0, kend, pre_mask, filt_mask, [&](int k, int* spec, int* pin) { return *spec = task_spec[k], *pin = task_pin[k], true; },
+      [&](int k, int rep, int binder, u64 fits, const NodeRegs&, int) {
+        i64 sum = rep;
+        int mx = rep;
 #pragma unroll
-      for (int off = kWave / 2; off > 0; off >>= 1) {
-        sum += (i64)__shfl_xor((long long)sum, off, kWave);
-        mx = max(mx, __shfl_xor(mx, off, kWave));
-      }
-      i64 mine = lane == 0 ? sum : lane == 1 ? (i64)__popcll(fits) : 0;
-      {
-        const int c = __popcll(__ballot(rep > 0 && binder == kBindSlots));
-        if (lane == kBindSlots) mine = c;
-      }
-      {
-        const int c = __popcll(__ballot(rep > 0 && binder == kBindPort));
-        if (lane == kBindPort) mine = c;
-      }
+        for (int off = kWave / 2; off > 0; off >>= 1) {
+          sum += (i64)__shfl_xor((long long)sum, off, kWave);
+          mx = max(mx, __shfl_xor(mx, off, kWave));
+        }
+        i64 mine = lane == 0 ? sum : lane == 1 ? (i64)__popcll(fits) : 0;
+        {
+          const int c = __popcll(__ballot(rep > 0 && binder == kBindSlots));
+          if (lane == kBindSlots) mine = c;
+        }
+        {
+          const int c = __popcll(__ballot(rep > 0 && binder == kBindPort));
+          if (lane == kBindPort) mine = c;
+        }
 #pragma unroll
-      for (int r = 0; r < kMaxR; ++r) {
-        const int c = __popcll(__ballot(rep > 0 && binder == kBindRes0 + r));
-        if (lane == kBindRes0 + r) mine = c;
-      }
-      if (lane < kHeadroomCells && mine) atomicAdd((u64*)&acc[(k - k0) * kHeadroomCells + lane], (u64)mine);
-      if (lane == 0) atomicMax(&accmax[k - k0], mx);
-    }
-  }
+        for (int r = 0; r < kMaxR; ++r) {
+          const int c = __popcll(__ballot(rep > 0 && binder == kBindRes0 + r));
+          if (lane == kBindRes0 + r) mine = c;
+        }
+        if (lane < kHeadroomCells && mine) atomicAdd((u64*)&acc[(k - k0) * kHeadroomCells + lane], (u64)mine);
+        if (lane == 0) atomicMax(&accmax[k - k0], mx);
+      });
   __syncthreads();
   for (int i = threadIdx.x; i < (kend - k0) * kHeadroomCells; i += kBlock) {
     const i64 v = acc[i];
@@ -3042,8 +3069,8 @@ __global__ __launch_bounds__(kBlock) void k_headroom(NodeTable t, SpecTable s, i
   if ((int)threadIdx.x < kend - k0) {
     const int v = accmax[threadIdx.x];
     if (v) atomicMax((long long*)&maxk[k0 + threadIdx.x], (long long)v);
-    if (blockIdx.y == 0 && (s.flags[task_spec[k0 + threadIdx.x]] & kSpecUnsupported)) cells[(size_t)(k0 + threadIdx.x) * kHeadroomCells + 3] = 1;
   }
+  headroom_unsupported(s, k0, kend, [&](int k) { return task_spec[k]; }, cells + 3, kHeadroomCells);
 }
 
 // replicas of ONE ask on every node of the table (thread = node, as k_query_pod): which nodes take how many copies
@@ -3058,15 +3085,12 @@ __global__ __launch_bounds__(kBlock) void k_headroom_pod(NodeTable t, SpecTable 
 }
 
 // ykpred_headroom_groups: replicas summed per GROUP of nodes (a zone, a rack, a host): table[task][g][0] = Σ replicas over the nodes of
-// group g, [g][1] = how many of them take at least one copy; row G holds the nodes of no group (node_group[n] < 0). Grid and walk of
-// k_headroom: blockIdx.x = chunk of kExplainTasks tasks, blockIdx.y = 256 nodes, lane = node; the node columns and the lane's group id
-// are loaded once per chunk, the task data is wave-uniform, a wave in which no lane fits skips the task. Two accumulation forms:
+// group g, [g][1] = how many of them take at least one copy; row G holds the nodes of no group (node_group[n] < 0). The gather walk
+// (headroom_walk), the lane's group id loaded once per chunk. Two ACCUMULATION FORMS:
 //   use_lds  (a template parameter: two kernels, told apart in a trace) the chunk's [kExplainTasks][G + 1][2] table lives in dynamic
 //            LDS (G <= kGroupLdsMaxGroups): lanes add into LDS, the block flushes its non-zero cells with one global integer add each;
 //   else     (up to G == N, where nearly every lane owns its cell) the adds go straight to the global table.
 // A wave-level merge of lanes that share a group id was measured and did not pay: every fitting lane adds for itself.
-// Every add is an integer add: the result does not depend on the order of arrival. unsupported[task] = 1 for a spec the engine does not
-// evaluate (written by the first node group alone; every cell of such a task stays 0: eval_pair rejects every pair).
 constexpr int kGroupCells = 2;
 constexpr int kGroupSummary = 8;
 constexpr int kGroupLdsBytes = 32 * 1024;  // LDS budget of the few-groups form: five workgroups still share a CU's 160 KiB
@@ -3083,32 +3107,23 @@ __global__ __launch_bounds__(kBlock) void k_headroom_groups(NodeTable t, SpecTab
     for (int i = threadIdx.x; i < (kend - k0) * row_cells; i += kBlock) gacc[i] = 0;
     __syncthreads();
   }
-  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-  int n = (blockIdx.y * kWavesPerBlock + wave) * kWave + lane;
-  const bool live = n < t.n;
-  if (!live) n = -1;
-  if (__ballot(live)) {  // (wave-uniform: a wave wholly past N skips the walk, not the barriers)
-    NodeRegs nr;
-    load_node(t, n, &nr);
-    const i64 slots = live ? (i64)t.allowed[n] - (i64)t.count[n] : 0;
-    int g = live ? node_group[n] : -1;
-    if (g < 0) g = G;
-    for (int k = k0; k < kend; ++k) {
-      int binder = 0;
-      const int rep = live ? replicas(s, task_spec[k], task_pin[k], n, nr, slots, pre_mask, filt_mask, &binder) : 0;
-      if (!__ballot(rep > 0)) continue;  // (wave-uniform: no lane fits)
-      if (rep <= 0) continue;
-      if (use_lds) {
-        i64* cell = gacc + (k - k0) * row_cells + g * kGroupCells;
-        atomicAdd((u64*)&cell[0], (u64)rep);
-        atomicAdd((u64*)&cell[1], (u64)1);
-      } else {
-        i64* cell = table + (size_t)k * row_cells + g * kGroupCells;
-        atomicAdd((u64*)&cell[0], (u64)rep);
-        atomicAdd((u64*)&cell[1], (u64)1);
-      }
-    }
-  }
+  bool live;
+  const int n = headroom_node(t, &live);
+  int g = live ? node_group[n] : -1;
+  if (g < 0) g = G;
+  headroom_walk<false>(
+      t, s, k0, kend, pre_mask, filt_mask, [&](int k, int* spec, int* pin) { return *spec = task_spec[k], *pin = task_pin[k], true; },
+      [&](int k, int rep, int, u64, const NodeRegs&, int) {
+        if (use_lds) {
+          i64* cell = gacc + (k - k0) * row_cells + g * kGroupCells;
+          atomicAdd((u64*)&cell[0], (u64)rep);
+          atomicAdd((u64*)&cell[1], (u64)1);
+        } else {
+          i64* cell = table + (size_t)k * row_cells + g * kGroupCells;
+          atomicAdd((u64*)&cell[0], (u64)rep);
+          atomicAdd((u64*)&cell[1], (u64)1);
+        }
+      });
   if (use_lds) {
     __syncthreads();
     for (int i = threadIdx.x; i < (kend - k0) * row_cells; i += kBlock) {
@@ -3116,7 +3131,7 @@ __global__ __launch_bounds__(kBlock) void k_headroom_groups(NodeTable t, SpecTab
       if (v) atomicAdd((u64*)&table[(size_t)k0 * row_cells + i], (u64)v);
     }
   }
-  if (blockIdx.y == 0 && (int)threadIdx.x < kend - k0 && (s.flags[task_spec[k0 + threadIdx.x]] & kSpecUnsupported)) unsupported[k0 + threadIdx.x] = 1;
+  headroom_unsupported(s, k0, kend, [&](int k) { return task_spec[k]; }, unsupported, 1);
 }
 
 // The summary of one (task, want) over that task's G group rows, one wave per pair, after the table is complete (on a sharded engine:
@@ -3176,21 +3191,53 @@ __global__ __launch_bounds__(kBlock) void k_group_summary(int n_pairs, const int
   }
 }
 
+// The accumulation of the two gathers over RAGGED DOMAIN ROWS (k_headroom_spread, k_headroom_affinity): per task and row the pair
+// (Σ replicas, nodes), added into cells [1], [2] of the task's { cnt, cap, nodes, copies } table rows. Two forms, as k_headroom_groups:
+//   use_lds  every task of the launch has dom_size <= kGroupLdsMaxGroups: the chunk's [kExplainTasks][kSpreadLdsRows][2] cells live in
+//            static LDS (the kernel's `sacc`), the block flushes its non-zero cells with one global integer add each — row_of(task,
+//            LDS row) names the table row;
+//   else     the adds go straight to the global table.
+// `sacc` is handed to the three routines as the kernel's own array, not kept in a struct: behind a stored pointer the compiler no longer
+// sees an LDS address, an LDS add becomes a flat one, and every wave-uniform task load behind it a vector load.
+constexpr int kSpreadRowCells = 4;  // cnt, cap, nodes, copies
+constexpr int kSpreadLdsRows = kGroupLdsMaxGroups + 1;
+template <bool use_lds>
+__device__ __forceinline__ void domain_acc_zero(i64* sacc, int k0, int kend) {
+  if (!use_lds) return;
+  for (int i = threadIdx.x; i < (kend - k0) * kSpreadLdsRows * 2; i += kBlock) sacc[i] = 0;
+  __syncthreads();
+}
+// a node that takes rep copies of the chunk's task kk: LDS row `lds_row` of the task, or table row `table_row`
+template <bool use_lds>
+__device__ __forceinline__ void domain_acc_add(i64* sacc, i64* __restrict__ table, int kk, int lds_row, size_t table_row, int rep) {
+  if (use_lds) {
+    i64* cell = sacc + (kk * kSpreadLdsRows + lds_row) * 2;
+    atomicAdd((u64*)&cell[0], (u64)rep);
+    atomicAdd((u64*)&cell[1], (u64)1);
+  } else {
+    i64* cell = table + table_row * kSpreadRowCells;
+    atomicAdd((u64*)&cell[1], (u64)rep);
+    atomicAdd((u64*)&cell[2], (u64)1);
+  }
+}
+template <bool use_lds, class RowOf>
+__device__ __forceinline__ void domain_acc_flush(const i64* sacc, i64* __restrict__ table, int k0, int kend, RowOf row_of) {
+  if (!use_lds) return;
+  __syncthreads();
+  for (int i = threadIdx.x; i < (kend - k0) * kSpreadLdsRows * 2; i += kBlock) {
+    const i64 v = sacc[i];  // (non-zero only in rows the task uses)
+    if (v) atomicAdd((u64*)&table[row_of(k0 + i / (kSpreadLdsRows * 2), (i / 2) % kSpreadLdsRows) * kSpreadRowCells + 1 + (i & 1)], (u64)v);
+  }
+}
+
 // ykpred_headroom_spread: headroom of an ask whose ONE live topology constraint is a hard PodTopologySpread constraint c (the host decides
 // that from the signature tables). Copies then interact only through c's histogram row, and the sequential loop over copies has a closed
-// result per DOMAIN of c's key. This kernel gathers its inputs: table[row0 + d] = { cnt, cap, nodes, copies } per domain
-// d, of which it adds cap = Σ replicas over the COUNTING nodes of the domain and nodes = how many of them take a copy; replicas is
-// ykpred_headroom's routine, called under the Filter mask WITHOUT the spread bit (the caller passes it so). A node without the label takes
-// no copy (the Filter fails it) and adds nothing. A node that takes a copy, carries the label and does NOT count for c (an inclusion
-// policy of c fails on it while the plugin lists do not filter it out) raises noncounting[task]: the loop's result then depends on the
-// node order, the task stays coupled. Grid and walk of k_headroom_groups: blockIdx.x = chunk of kExplainTasks tasks, blockIdx.y = 256
-// nodes, lane = node; node columns once per chunk, task data wave-uniform, a wave in which no lane fits skips the task. The lane's
-// domain id is the resident NodeTable.domain column (in NodeRegs). Two accumulation forms, as k_headroom_groups:
-//   use_lds  every task of the launch has dom_size <= kGroupLdsMaxGroups: the chunk's [kExplainTasks][kSpreadLdsRows][2] cells live in
-//            LDS, the block flushes its non-zero cells with one global integer add each;
-//   else     the adds go straight to the global table.
-// Integer adds only: the result does not depend on the order of arrival. A task with g < 0 does not qualify by its signature and is
-// skipped. unsupported[task] = 1 for a spec the engine does not evaluate (first node group alone).
+// result per DOMAIN of c's key. This kernel gathers its inputs (headroom_walk, domain_acc_*): cap = Σ replicas over the
+// COUNTING nodes of the domain and nodes = how many of them take a copy; replicas is ykpred_headroom's routine, called under the Filter
+// mask WITHOUT the spread bit (the caller passes it so). Its rule: a node without the label takes no copy (the Filter fails it) and adds
+// nothing. A node that takes a copy, carries the label and does NOT count for c (an inclusion policy of c fails on it while the plugin
+// lists do not filter it out) raises noncounting[task]: the loop's result then depends on the node order, the task stays coupled. A
+// task with g < 0 does not qualify by its signature and is skipped.
 struct SpreadHeadTask {
   int spec, pin;  // the task
   int sig, g;     // its topology signature and the row of its one live constraint in SpreadSigs.c; g = -1: does not qualify
@@ -3199,8 +3246,6 @@ struct SpreadHeadTask {
   int pad;
 };
 constexpr int kSpreadHeadCells = 16;
-constexpr int kSpreadRowCells = 4;  // cnt, cap, nodes, copies
-constexpr int kSpreadLdsRows = kGroupLdsMaxGroups + 1;
 template <bool use_lds>
 __global__ __launch_bounds__(kBlock) void k_headroom_spread(NodeTable t, SpecTable s, AffSigs sig_aff, const u64* __restrict__ sig_tol, int n_tasks,
                                                             const SpreadHeadTask* __restrict__ tasks, unsigned pre_mask, unsigned filt_mask,
@@ -3208,58 +3253,29 @@ __global__ __launch_bounds__(kBlock) void k_headroom_spread(NodeTable t, SpecTab
                                                             i64* __restrict__ unsupported) {
   __shared__ i64 sacc[use_lds ? kExplainTasks * kSpreadLdsRows * 2 : 1];
   const int k0 = blockIdx.x * kExplainTasks, kend = min(k0 + kExplainTasks, n_tasks);
-  if (use_lds) {
-    for (int i = threadIdx.x; i < (kend - k0) * kSpreadLdsRows * 2; i += kBlock) sacc[i] = 0;
-    __syncthreads();
-  }
-  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-  int n = (blockIdx.y * kWavesPerBlock + wave) * kWave + lane;
-  const bool live = n < t.n;
-  if (!live) n = -1;
-  if (__ballot(live)) {  // (wave-uniform: a wave wholly past N skips the walk, not the barriers)
-    NodeRegs nr;
-    load_node(t, n, &nr);
-    const i64 slots = live ? (i64)t.allowed[n] - (i64)t.count[n] : 0;
-    for (int k = k0; k < kend; ++k) {
-      const SpreadHeadTask tk = tasks[k];
-      if (tk.g < 0) continue;  // (wave-uniform)
-      int binder = 0;
-      const int rep = live ? replicas(s, tk.spec, tk.pin, n, nr, slots, pre_mask, filt_mask, &binder) : 0;
-      if (!__ballot(rep > 0)) continue;  // (wave-uniform: no lane fits)
-      if (rep <= 0) continue;
-      const SpreadC c = s.spread.c[tk.g];
-      int dm = -1;
+  domain_acc_zero<use_lds>(sacc, k0, kend);
+  SpreadHeadTask tk;
+  headroom_walk<false>(
+      t, s, k0, kend, pre_mask, filt_mask, [&](int k, int* spec, int* pin) { return tk = tasks[k], *spec = tk.spec, *pin = tk.pin, tk.g >= 0; },
+      [&](int k, int rep, int, u64, const NodeRegs& nr, int n) {
+        const SpreadC c = s.spread.c[tk.g];
+        int dm = -1;
 #pragma unroll
-      for (int kd = 0; kd < kMaxKD; ++kd)
-        if (kd == c.kd) dm = nr.dom[kd];
-      if (dm < 0 || dm >= c.dom_size) continue;  // the label is missing: PodTopologySpread fails the node, it takes no copy
-      // A fitting lane has passed NodeAffinity's Filter (the DNF the Honor policy reads) when that plugin is in the Filter list, and
-      // TaintToleration's likewise: the inclusion policies are evaluated only for a policy whose plugin is missing (wave-uniform).
-      const bool ask_aff = (c.flags & kSpreadHonorAffinity) && !(filt_mask & kPlugAffinity);
-      const bool ask_tol = (c.flags & kSpreadHonorTaints) && !(filt_mask & kPlugTaint);
-      if ((ask_aff || ask_tol) && !spread_counts_here(c, spread_eligibility(t, s.spread, sig_aff, sig_tol, tk.sig, n))) {
-        atomicAdd((u64*)&noncounting[k], (u64)1);
-        continue;
-      }
-      if (use_lds) {
-        i64* cell = sacc + ((k - k0) * kSpreadLdsRows + dm) * 2;
-        atomicAdd((u64*)&cell[0], (u64)rep);
-        atomicAdd((u64*)&cell[1], (u64)1);
-      } else {
-        i64* cell = table + ((size_t)tk.row0 + dm) * kSpreadRowCells;
-        atomicAdd((u64*)&cell[1], (u64)rep);
-        atomicAdd((u64*)&cell[2], (u64)1);
-      }
-    }
-  }
-  if (use_lds) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < (kend - k0) * kSpreadLdsRows * 2; i += kBlock) {
-      const i64 v = sacc[i];  // (non-zero only in rows below the task's dom_size)
-      if (v) atomicAdd((u64*)&table[((size_t)tasks[k0 + i / (kSpreadLdsRows * 2)].row0 + (i / 2) % kSpreadLdsRows) * kSpreadRowCells + 1 + (i & 1)], (u64)v);
-    }
-  }
-  if (blockIdx.y == 0 && (int)threadIdx.x < kend - k0 && (s.flags[tasks[k0 + threadIdx.x].spec] & kSpecUnsupported)) unsupported[k0 + threadIdx.x] = 1;
+        for (int kd = 0; kd < kMaxKD; ++kd)
+          if (kd == c.kd) dm = nr.dom[kd];
+        if (dm < 0 || dm >= c.dom_size) return;  // the label is missing: PodTopologySpread fails the node, it takes no copy
+        // A fitting lane has passed NodeAffinity's Filter (the DNF the Honor policy reads) when that plugin is in the Filter list, and
+        // TaintToleration's likewise: the inclusion policies are evaluated only for a policy whose plugin is missing (wave-uniform).
+        const bool ask_aff = (c.flags & kSpreadHonorAffinity) && !(filt_mask & kPlugAffinity);
+        const bool ask_tol = (c.flags & kSpreadHonorTaints) && !(filt_mask & kPlugTaint);
+        if ((ask_aff || ask_tol) && !spread_counts_here(c, spread_eligibility(t, s.spread, sig_aff, sig_tol, tk.sig, n))) {
+          atomicAdd((u64*)&noncounting[k], (u64)1);
+          return;
+        }
+        domain_acc_add<use_lds>(sacc, table, k - k0, dm, (size_t)tk.row0 + dm, rep);
+      });
+  domain_acc_flush<use_lds>(sacc, table, k0, kend, [&](int k, int r) { return (size_t)tasks[k].row0 + r; });
+  headroom_unsupported(s, k0, kend, [&](int k) { return tasks[k].spec; }, unsupported, 1);
 }
 
 // The fill of one task over its domain rows, one wave per task, after the table is complete (on a sharded engine: after the all-reduce;
@@ -3358,19 +3374,11 @@ __global__ __launch_bounds__(kBlock) void k_spread_fill(int n_tasks, const Sprea
 // ykpred_headroom_affinity: headroom of an ask whose live topology constraints are all of the InterPodAffinity kinds.
 // Copies then interact only through the histogram rows of the anti-affinity terms they themselves add to, all on ONE topology key (the
 // host decides that from the signature tables and the spec effects), and the sequential loop over copies has a closed result per DOMAIN
-// of that key. This kernel gathers its inputs: table[row0 + d] = { cnt, cap, nodes, copies } per domain d of the task's key, of which it
-// adds cap = Σ replicas over the nodes of the domain and nodes = how many of them take a copy; replicas is ykpred_headroom's routine
-// under the caller's lists, InterPodAffinity included: the pair's verdict is the static one against the current histograms. A node
-// WITHOUT the key is not dropped — an anti-affinity row passes it and a copy placed there moves no cell — it adds to the task's OUTSIDE
-// row, table[row0 + dom_size]. Grid and walk of k_headroom_spread: blockIdx.x = chunk of kExplainTasks tasks, blockIdx.y = 256 nodes,
-// lane = node; node columns once per chunk, task data wave-uniform, a wave in which no lane fits skips the task; the lane's domain id is
-// the resident NodeRegs.dom. Two accumulation forms:
-//   use_lds  every task of the launch has dom_size <= kGroupLdsMaxGroups: the chunk's [kExplainTasks][kSpreadLdsRows][2] cells live in
-//            LDS, row kGroupLdsMaxGroups of a task serving as its outside row; the block flushes its non-zero cells with one global
-//            integer add each;
-//   else     the adds go straight to the global table.
-// Integer adds only: the result does not depend on the order of arrival. A task with kd < 0 does not qualify by its signature and is
-// skipped. unsupported[task] = 1 for a spec the engine does not evaluate (first node group alone).
+// of that key. This kernel gathers its inputs (headroom_walk, domain_acc_*): cap = Σ replicas over the nodes of the domain and nodes = how
+// many of them take a copy; replicas is ykpred_headroom's routine under the caller's lists, InterPodAffinity included: the pair's verdict
+// is the static one against the current histograms. Its rule: a node WITHOUT the key is not dropped — an anti-affinity row passes it and
+// a copy placed there moves no cell — it adds to the task's OUTSIDE row, table[row0 + dom_size]; in LDS, row kGroupLdsMaxGroups of the
+// task. A task with kd < 0 does not qualify by its signature and is skipped.
 struct AffHeadTask {
   int spec, pin;   // the task
   int sig, kd;     // its topology signature and the topology key its rows lie on; kd = -1: does not qualify, no rows
@@ -3387,52 +3395,23 @@ __global__ __launch_bounds__(kBlock) void k_headroom_affinity(NodeTable t, SpecT
                                                               i64* __restrict__ unsupported) {
   __shared__ i64 sacc[use_lds ? kExplainTasks * kSpreadLdsRows * 2 : 1];
   const int k0 = blockIdx.x * kExplainTasks, kend = min(k0 + kExplainTasks, n_tasks);
-  if (use_lds) {
-    for (int i = threadIdx.x; i < (kend - k0) * kSpreadLdsRows * 2; i += kBlock) sacc[i] = 0;
-    __syncthreads();
-  }
-  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-  int n = (blockIdx.y * kWavesPerBlock + wave) * kWave + lane;
-  const bool live = n < t.n;
-  if (!live) n = -1;
-  if (__ballot(live)) {  // (wave-uniform: a wave wholly past N skips the walk, not the barriers)
-    NodeRegs nr;
-    load_node(t, n, &nr);
-    const i64 slots = live ? (i64)t.allowed[n] - (i64)t.count[n] : 0;
-    for (int k = k0; k < kend; ++k) {
-      const AffHeadTask tk = tasks[k];
-      if (tk.kd < 0) continue;  // (wave-uniform)
-      int binder = 0;
-      const int rep = live ? replicas(s, tk.spec, tk.pin, n, nr, slots, pre_mask, filt_mask, &binder) : 0;
-      if (!__ballot(rep > 0)) continue;  // (wave-uniform: no lane fits)
-      if (rep <= 0) continue;
-      int dm = -1;
+  domain_acc_zero<use_lds>(sacc, k0, kend);
+  AffHeadTask tk;
+  headroom_walk<false>(
+      t, s, k0, kend, pre_mask, filt_mask, [&](int k, int* spec, int* pin) { return tk = tasks[k], *spec = tk.spec, *pin = tk.pin, tk.kd >= 0; },
+      [&](int k, int rep, int, u64, const NodeRegs& nr, int) {
+        int dm = -1;
 #pragma unroll
-      for (int kd = 0; kd < kMaxKD; ++kd)
-        if (kd == tk.kd) dm = nr.dom[kd];
-      const bool inside = dm >= 0 && dm < tk.dom_size;
-      if (use_lds) {
-        i64* cell = sacc + ((k - k0) * kSpreadLdsRows + (inside ? dm : kGroupLdsMaxGroups)) * 2;
-        atomicAdd((u64*)&cell[0], (u64)rep);
-        atomicAdd((u64*)&cell[1], (u64)1);
-      } else {
-        i64* cell = table + ((size_t)tk.row0 + (inside ? dm : tk.dom_size)) * kSpreadRowCells;
-        atomicAdd((u64*)&cell[1], (u64)rep);
-        atomicAdd((u64*)&cell[2], (u64)1);
-      }
-    }
-  }
-  if (use_lds) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < (kend - k0) * kSpreadLdsRows * 2; i += kBlock) {
-      const i64 v = sacc[i];  // (non-zero only in rows below the task's dom_size and in its outside row)
-      if (!v) continue;
-      const AffHeadTask tk = tasks[k0 + i / (kSpreadLdsRows * 2)];
-      const int r = (i / 2) % kSpreadLdsRows;
-      atomicAdd((u64*)&table[((size_t)tk.row0 + (r == kGroupLdsMaxGroups ? tk.dom_size : r)) * kSpreadRowCells + 1 + (i & 1)], (u64)v);
-    }
-  }
-  if (blockIdx.y == 0 && (int)threadIdx.x < kend - k0 && (s.flags[tasks[k0 + threadIdx.x].spec] & kSpecUnsupported)) unsupported[k0 + threadIdx.x] = 1;
+        for (int kd = 0; kd < kMaxKD; ++kd)
+          if (kd == tk.kd) dm = nr.dom[kd];
+        const bool inside = dm >= 0 && dm < tk.dom_size;
+        domain_acc_add<use_lds>(sacc, table, k - k0, inside ? dm : kGroupLdsMaxGroups, (size_t)tk.row0 + (inside ? dm : tk.dom_size), rep);
+      });
+  domain_acc_flush<use_lds>(sacc, table, k0, kend, [&](int k, int r) {
+    const AffHeadTask f = tasks[k];
+    return (size_t)f.row0 + (r == kGroupLdsMaxGroups ? f.dom_size : r);
+  });
+  headroom_unsupported(s, k0, kend, [&](int k) { return tasks[k].spec; }, unsupported, 1);
 }
 
 // The fill of one task over its domain rows after the table is complete (on a sharded engine: after the all-reduce; the histograms are

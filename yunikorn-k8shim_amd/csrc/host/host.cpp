@@ -3369,29 +3369,45 @@ int64_t ykhost_explain_message(ykhost_t* h, const char* allocation_key, int32_t 
   return ykhost_explain_format(h, bins, out, len);
 }
 
-// ---- how many copies of an ask the cluster still takes (ykpred_headroom) -----------------------------------------------------------
+// ---- how many copies of an ask the cluster still takes (ykpred_headroom and its spread / affinity fallbacks) -----------------------------
 // The allocation-phase lists always: the reservation lists carry no NodeResourcesFit, and without it nothing bounds the count.
-int32_t ykhost_headroom(ykhost_t* h, int32_t n, const int32_t* asks, int64_t* out_cells) {
-  YKHOST_LOCKED(h);
-  if (n < 0 || (n > 0 && !out_cells)) return fail(h, "headroom: bad argument", -1);
+namespace {
+// the label values of topology key k in domain-id order (the encoder's ids: the ranks of the bytewise-sorted values it knows)
+std::vector<std::string> spread_domain_values(const ykhost* h, int64_t k) {
+  std::vector<std::string> values;
+  if (k < 0 || (size_t)k >= h->enc.domain_ids.size()) return values;
+  values.resize(h->enc.domain_ids[(size_t)k].size());
+  for (const auto& kv : h->enc.domain_ids[(size_t)k])
+    if (kv.second >= 0 && (size_t)kv.second < values.size()) values[(size_t)kv.second] = kv.first;
+  return values;
+}
+
+using HeadroomListCall = int32_t (*)(ykpred_engine_t*, int32_t, const int32_t*, uint32_t, uint32_t, int64_t*);
+using HeadroomRowsCall = int32_t (*)(ykpred_engine_t*, int32_t, uint32_t, uint32_t, int32_t, int64_t*, int32_t*);
+
+// The LIST call behind ykhost_headroom, ykhost_headroom_spread and ykhost_headroom_affinity: `cells` per ask, status in cell [3].
+// `after_sync` (may be null) runs once the tables are synced. An ask routed to the CPU manager gets status 1 without a device call; on
+// a node-sharded handle every ask goes to the engine, as in ykhost_explain (the call is collective and the shards' dictionaries may
+// route different asks), and — unless `check_sharded` — so do the indices: the engine's agreement step gives every rank the same error.
+int headroom_list(ykhost* h, const std::string& name, size_t cells, bool check_sharded, int (*after_sync)(ykhost*), HeadroomListCall call,
+                  int32_t n, const int32_t* asks, int64_t* out_cells) {
+  if (n < 0 || (n > 0 && !out_cells)) return fail(h, name + ": bad argument", -1);
   if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
   int rc = sync(h);
   if (rc) return rc;
-  const int P = (int)h->pending.size();
-  for (int i = 0; i < n; ++i)
-    if ((asks ? asks[i] : i) < 0 || (asks ? asks[i] : i) >= P) return fail(h, "headroom: ask index out of range", YKPRED_E_INVALID);
-  // An ask routed to the CPU manager gets status 1 without a device call; on a node-sharded handle every ask goes to the engine, as in
-  // ykhost_explain (the call is collective and the shards' dictionaries may route different asks).
+  if (after_sync && (rc = after_sync(h))) return rc;
   int32_t world = 1;
   ykpred_comm_info(h->eng, nullptr, &world, nullptr);
+  const int P = (int)h->pending.size();
+  if (check_sharded || world <= 1)
+    for (int i = 0; i < n; ++i)
+      if ((asks ? asks[i] : i) < 0 || (asks ? asks[i] : i) >= P) return fail(h, name + ": ask index out of range", YKPRED_E_INVALID);
   std::vector<int32_t> list, slot;
-  list.reserve((size_t)n);
-  slot.reserve((size_t)n);
   for (int i = 0; i < n; ++i) {
     const int row = asks ? asks[i] : i;
-    int64_t* c = out_cells + (size_t)i * YKPRED_HEADROOM_CELLS;
+    int64_t* c = out_cells + (size_t)i * cells;
     if (world <= 1 && h->enc.unsupported.count(h->pending[(size_t)row]->tpl)) {
-      std::fill(c, c + YKPRED_HEADROOM_CELLS, (int64_t)0);
+      std::fill(c, c + cells, (int64_t)0);
       c[3] = 1;
     } else {
       list.push_back(row);
@@ -3399,12 +3415,79 @@ int32_t ykhost_headroom(ykhost_t* h, int32_t n, const int32_t* asks, int64_t* ou
     }
   }
   if (list.empty() && world <= 1) return 0;
-  std::vector<int64_t> rows(list.size() * (size_t)YKPRED_HEADROOM_CELLS);
-  rc = ykpred_headroom(h->eng, (int32_t)list.size(), list.data(), h->alloc_pre, h->alloc_filt, rows.data());
-  if (rc) return fail(h, std::string("ykpred_headroom: ") + ykpred_last_error(h->eng), rc);
-  for (size_t k = 0; k < list.size(); ++k)
-    memcpy(out_cells + (size_t)slot[k] * YKPRED_HEADROOM_CELLS, rows.data() + k * YKPRED_HEADROOM_CELLS, YKPRED_HEADROOM_CELLS * sizeof(int64_t));
+  std::vector<int64_t> rows(list.size() * cells);
+  rc = call(h->eng, (int32_t)list.size(), list.data(), h->alloc_pre, h->alloc_filt, rows.data());
+  if (rc) return fail(h, "ykpred_" + name + ": " + ykpred_last_error(h->eng), rc);
+  for (size_t k = 0; k < list.size(); ++k) memcpy(out_cells + (size_t)slot[k] * cells, rows.data() + k * cells, cells * sizeof(int64_t));
   return 0;
+}
+
+// The per-domain rows of ONE ask behind ykhost_headroom_spread_domains and ykhost_headroom_affinity_domains: the list call for the
+// summary, then — at a status with rows (0, and 4 where `status4_rows`) — the engine's rows and the domains' label values as JSON.
+int headroom_rows(ykhost* h, const std::string& name, bool status4_rows, int32_t (*list)(ykhost_t*, int32_t, const int32_t*, int64_t*),
+                  HeadroomRowsCall rows_call, int32_t pod, int64_t* out_summary, int64_t* out_rows, int32_t max_domains, char* values,
+                  int64_t values_len) {
+  copy_out("[]", values, values_len);
+  int rc = list(h, 1, &pod, out_summary);
+  if (rc) return rc;
+  if (out_summary[3] != 0 && !(status4_rows && out_summary[3] == 4)) return 0;
+  int32_t D = 0;
+  rc = rows_call(h->eng, pod, h->alloc_pre, h->alloc_filt, max_domains, out_rows, &D);
+  if (rc == YKPRED_E_INVALID && D > max_domains) return D;  // (the size needed, as ykhost_explain_format reports a length)
+  if (rc) return fail(h, "ykpred_" + name + "_pod: " + ykpred_last_error(h->eng), rc);
+  const std::vector<std::string> names = spread_domain_values(h, out_summary[12]);
+  std::string o = "[";
+  for (int32_t d = 0; d < D; ++d) {
+    if (d) o += ',';
+    js_str(o, (size_t)d < names.size() ? names[(size_t)d] : std::string());
+  }
+  o += ']';
+  copy_out(o, values, values_len);
+  return D;
+}
+
+// An ask named as the core names it (allocation key = pod UID) → its row, synced and evaluated by the engine; else the status the
+// *_by_key call returns. A routed ask sets *status_cell = 1.
+int ask_row_by_key(ykhost* h, const char* allocation_key, int64_t* status_cell, int32_t* row) {
+  ensure_uid_index(h);
+  auto it = h->by_uid.find(allocation_key ? allocation_key : "");
+  if (it == h->by_uid.end()) return YKHOST_E_POD_NOT_FOUND;
+  if (!it->second->ask) return fail(h, "pod holds no ask row", YKHOST_E_NOT_AN_ASK);
+  if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
+  const int rc = sync(h);
+  if (rc) return rc;
+  auto un = h->enc.unsupported.find(it->second->tpl);
+  if (un != h->enc.unsupported.end()) {
+    *status_cell = 1;
+    return fail(h, "ask is not evaluated by the engine (route it to the CPU predicate manager): " + un->second, YKHOST_E_UNSUPPORTED);
+  }
+  *row = it->second->row;
+  return 0;
+}
+
+// One ask by its allocation key, one crossing, behind the three *_by_key calls: the 16 cells of `list` and — where `best` is given —
+// the domain with the most copies ([11], of key [12]) as a label value, at status 0 (and 4 where `status4_rows`).
+int headroom_by_key(ykhost* h, const std::string& name, bool status4_rows, int32_t (*list)(ykhost_t*, int32_t, const int32_t*, int64_t*),
+                    const char* allocation_key, int64_t* out16, char* best, int64_t best_len) {
+  if (!out16) return fail(h, name + "_by_key: bad argument", -1);
+  std::fill(out16, out16 + 16, (int64_t)0);
+  copy_out("", best, best_len);
+  int32_t row = -1;
+  int rc = ask_row_by_key(h, allocation_key, &out16[3], &row);
+  if (rc) return rc;
+  rc = list(h, 1, &row, out16);
+  if (rc || !best) return rc;
+  if ((out16[3] == 0 || (status4_rows && out16[3] == 4)) && out16[11] >= 0) {
+    const std::vector<std::string> names = spread_domain_values(h, out16[12]);
+    if ((size_t)out16[11] < names.size()) copy_out(names[(size_t)out16[11]], best, best_len);
+  }
+  return 0;
+}
+}  // namespace
+
+int32_t ykhost_headroom(ykhost_t* h, int32_t n, const int32_t* asks, int64_t* out_cells) {
+  YKHOST_LOCKED(h);
+  return headroom_list(h, "headroom", YKPRED_HEADROOM_CELLS, true, nullptr, ykpred_headroom, n, asks, out_cells);
 }
 
 int32_t ykhost_headroom_nodes(ykhost_t* h, int32_t pod, int32_t* out) {
@@ -3422,22 +3505,7 @@ int32_t ykhost_headroom_nodes(ykhost_t* h, int32_t pod, int32_t* out) {
 // One ask named as the core names it (allocation key = pod UID): the figure for a task group, asked for one of its placeholders.
 int32_t ykhost_headroom_by_key(ykhost_t* h, const char* allocation_key, int64_t* out16) {
   YKHOST_LOCKED(h);
-  if (!out16) return fail(h, "headroom_by_key: bad argument", -1);
-  std::fill(out16, out16 + YKPRED_HEADROOM_CELLS, (int64_t)0);
-  ensure_uid_index(h);
-  auto it = h->by_uid.find(allocation_key ? allocation_key : "");
-  if (it == h->by_uid.end()) return YKHOST_E_POD_NOT_FOUND;
-  if (!it->second->ask) return fail(h, "pod holds no ask row", YKHOST_E_NOT_AN_ASK);
-  if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
-  int rc = sync(h);
-  if (rc) return rc;
-  auto un = h->enc.unsupported.find(it->second->tpl);
-  if (un != h->enc.unsupported.end()) {
-    out16[3] = 1;
-    return fail(h, "ask is not evaluated by the engine (route it to the CPU predicate manager): " + un->second, YKHOST_E_UNSUPPORTED);
-  }
-  const int32_t row = it->second->row;
-  return ykhost_headroom(h, 1, &row, out16);
+  return headroom_by_key(h, "headroom", false, ykhost_headroom, allocation_key, out16, nullptr, 0);
 }
 
 // ---- headroom per topology domain (ykpred_headroom_groups) --------------------------------------------------------------------------
@@ -3592,19 +3660,9 @@ int32_t ykhost_headroom_domain_by_key(ykhost_t* h, const char* allocation_key, c
   std::fill(out_summary, out_summary + YKPRED_GROUP_SUMMARY, (int64_t)0);
   copy_out("", best, best_len);
   copy_out("", tightest, tightest_len);
-  ensure_uid_index(h);
-  auto it = h->by_uid.find(allocation_key ? allocation_key : "");
-  if (it == h->by_uid.end()) return YKHOST_E_POD_NOT_FOUND;
-  if (!it->second->ask) return fail(h, "pod holds no ask row", YKHOST_E_NOT_AN_ASK);
-  if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
-  int rc = sync(h);
+  int32_t row = -1;
+  int rc = ask_row_by_key(h, allocation_key, &out_summary[0], &row);
   if (rc) return rc;
-  auto un = h->enc.unsupported.find(it->second->tpl);
-  if (un != h->enc.unsupported.end()) {
-    out_summary[0] = 1;
-    return fail(h, "ask is not evaluated by the engine (route it to the CPU predicate manager): " + un->second, YKHOST_E_UNSUPPORTED);
-  }
-  const int32_t row = it->second->row;
   rc = ykhost_headroom_domains(h, 1, &row, &want, label_key, out_summary, nullptr, 0);
   if (rc < 0) return rc;
   if (!h->domain_values_last) return 0;
@@ -3615,197 +3673,48 @@ int32_t ykhost_headroom_domain_by_key(ykhost_t* h, const char* allocation_key, c
 }
 
 // ---- headroom of asks with one hard spread constraint (ykpred_headroom_spread) ----------------------------------------------------------
-// The fallback when ykhost_headroom reports an ask as coupled. Always the ALLOCATION-phase plugin lists. Domain ids are the encoder's:
-// per topology key the ranks of the bytewise-sorted label values it knows (enc.domain_ids).
+// The fallback when ykhost_headroom reports an ask as coupled. Domain ids are the encoder's (spread_domain_values).
 int32_t ykhost_headroom_spread(ykhost_t* h, int32_t n, const int32_t* asks, int64_t* out_cells) {
   YKHOST_LOCKED(h);
-  if (n < 0 || (n > 0 && !out_cells)) return fail(h, "headroom_spread: bad argument", -1);
-  if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
-  int rc = sync(h);
-  if (rc) return rc;
-  int32_t world = 1;
-  ykpred_comm_info(h->eng, nullptr, &world, nullptr);
-  const int P = (int)h->pending.size();
-  // (on a node-sharded handle the engine checks the indices: its agreement step gives every rank the same error)
-  if (world <= 1)
-    for (int i = 0; i < n; ++i)
-      if ((asks ? asks[i] : i) < 0 || (asks ? asks[i] : i) >= P) return fail(h, "headroom_spread: ask index out of range", YKPRED_E_INVALID);
-  std::vector<int32_t> list, slot;
-  for (int i = 0; i < n; ++i) {
-    const int row = asks ? asks[i] : i;
-    int64_t* c = out_cells + (size_t)i * YKPRED_SPREAD_HEADROOM_CELLS;
-    if (world <= 1 && h->enc.unsupported.count(h->pending[(size_t)row]->tpl)) {  // routed: status 1 without a device call
-      std::fill(c, c + YKPRED_SPREAD_HEADROOM_CELLS, (int64_t)0);
-      c[3] = 1;
-    } else {
-      list.push_back(row);
-      slot.push_back(i);
-    }
-  }
-  if (list.empty() && world <= 1) return 0;
-  std::vector<int64_t> rows(list.size() * (size_t)YKPRED_SPREAD_HEADROOM_CELLS);
-  rc = ykpred_headroom_spread(h->eng, (int32_t)list.size(), list.data(), h->alloc_pre, h->alloc_filt, rows.data());
-  if (rc) return fail(h, std::string("ykpred_headroom_spread: ") + ykpred_last_error(h->eng), rc);
-  for (size_t k = 0; k < list.size(); ++k)
-    memcpy(out_cells + (size_t)slot[k] * YKPRED_SPREAD_HEADROOM_CELLS, rows.data() + k * YKPRED_SPREAD_HEADROOM_CELLS,
-           YKPRED_SPREAD_HEADROOM_CELLS * sizeof(int64_t));
-  return 0;
+  return headroom_list(h, "headroom_spread", YKPRED_SPREAD_HEADROOM_CELLS, false, nullptr, ykpred_headroom_spread, n, asks, out_cells);
 }
-
-namespace {
-// the label values of topology key k in domain-id order
-std::vector<std::string> spread_domain_values(const ykhost* h, int64_t k) {
-  std::vector<std::string> values;
-  if (k < 0 || (size_t)k >= h->enc.domain_ids.size()) return values;
-  values.resize(h->enc.domain_ids[(size_t)k].size());
-  for (const auto& kv : h->enc.domain_ids[(size_t)k])
-    if (kv.second >= 0 && (size_t)kv.second < values.size()) values[(size_t)kv.second] = kv.first;
-  return values;
-}
-}  // namespace
 
 int32_t ykhost_headroom_spread_domains(ykhost_t* h, int32_t pod, int64_t* out_summary, int64_t* out_rows, int32_t max_domains, char* values,
                                        int64_t values_len) {
   YKHOST_LOCKED(h);
   if (!out_summary || max_domains < 0 || (max_domains > 0 && !out_rows)) return fail(h, "headroom_spread_domains: bad argument", -1);
-  copy_out("[]", values, values_len);
-  int rc = ykhost_headroom_spread(h, 1, &pod, out_summary);
-  if (rc) return rc;
-  if (out_summary[3] != 0) return 0;
-  int32_t D = 0;
-  rc = ykpred_headroom_spread_pod(h->eng, pod, h->alloc_pre, h->alloc_filt, max_domains, out_rows, &D);
-  if (rc == YKPRED_E_INVALID && D > max_domains) return D;  // (the size needed, as ykhost_explain_format reports a length)
-  if (rc) return fail(h, std::string("ykpred_headroom_spread_pod: ") + ykpred_last_error(h->eng), rc);
-  const std::vector<std::string> names = spread_domain_values(h, out_summary[12]);
-  std::string o = "[";
-  for (int32_t d = 0; d < D; ++d) {
-    if (d) o += ',';
-    js_str(o, (size_t)d < names.size() ? names[(size_t)d] : std::string());
-  }
-  o += ']';
-  copy_out(o, values, values_len);
-  return D;
+  return headroom_rows(h, "headroom_spread", false, ykhost_headroom_spread, ykpred_headroom_spread_pod, pod, out_summary, out_rows, max_domains,
+                       values, values_len);
 }
 
 // One ask named as the core names it, one crossing: the summary and the domain with the most copies as a label value.
 int32_t ykhost_headroom_spread_by_key(ykhost_t* h, const char* allocation_key, int64_t* out16, char* best, int64_t best_len) {
   YKHOST_LOCKED(h);
-  if (!out16) return fail(h, "headroom_spread_by_key: bad argument", -1);
-  std::fill(out16, out16 + YKPRED_SPREAD_HEADROOM_CELLS, (int64_t)0);
-  copy_out("", best, best_len);
-  ensure_uid_index(h);
-  auto it = h->by_uid.find(allocation_key ? allocation_key : "");
-  if (it == h->by_uid.end()) return YKHOST_E_POD_NOT_FOUND;
-  if (!it->second->ask) return fail(h, "pod holds no ask row", YKHOST_E_NOT_AN_ASK);
-  if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
-  int rc = sync(h);
-  if (rc) return rc;
-  auto un = h->enc.unsupported.find(it->second->tpl);
-  if (un != h->enc.unsupported.end()) {
-    out16[3] = 1;
-    return fail(h, "ask is not evaluated by the engine (route it to the CPU predicate manager): " + un->second, YKHOST_E_UNSUPPORTED);
-  }
-  const int32_t row = it->second->row;
-  rc = ykhost_headroom_spread(h, 1, &row, out16);
-  if (rc) return rc;
-  if (out16[3] == 0 && out16[11] >= 0) {
-    const std::vector<std::string> names = spread_domain_values(h, out16[12]);
-    if ((size_t)out16[11] < names.size()) copy_out(names[(size_t)out16[11]], best, best_len);
-  }
-  return 0;
+  return headroom_by_key(h, "headroom_spread", false, ykhost_headroom_spread, allocation_key, out16, best, best_len);
 }
 
 // ---- headroom of asks with required pod (anti-)affinity (ykpred_headroom_affinity) -------------------------------------------------------
-// The other fallback when ykhost_headroom reports an ask as coupled. Always the ALLOCATION-phase plugin lists. What a copy adds to the
-// histograms comes from the spec effects: uploaded here when the spec table moved since the last upload.
+// The other fallback when ykhost_headroom reports an ask as coupled. What a copy adds to the histograms comes from the spec effects:
+// uploaded here when the spec table moved since the last upload.
 int32_t ykhost_headroom_affinity(ykhost_t* h, int32_t n, const int32_t* asks, int64_t* out_cells) {
   YKHOST_LOCKED(h);
-  if (n < 0 || (n > 0 && !out_cells)) return fail(h, "headroom_affinity: bad argument", -1);
-  if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
-  int rc = sync(h);
-  if (rc) return rc;
-  rc = upload_spec_effects(h, true);
-  if (rc) return rc;
-  int32_t world = 1;
-  ykpred_comm_info(h->eng, nullptr, &world, nullptr);
-  const int P = (int)h->pending.size();
-  // (on a node-sharded handle the engine checks the indices: its agreement step gives every rank the same error)
-  if (world <= 1)
-    for (int i = 0; i < n; ++i)
-      if ((asks ? asks[i] : i) < 0 || (asks ? asks[i] : i) >= P) return fail(h, "headroom_affinity: ask index out of range", YKPRED_E_INVALID);
-  std::vector<int32_t> list, slot;
-  for (int i = 0; i < n; ++i) {
-    const int row = asks ? asks[i] : i;
-    int64_t* c = out_cells + (size_t)i * YKPRED_AFFINITY_HEADROOM_CELLS;
-    if (world <= 1 && h->enc.unsupported.count(h->pending[(size_t)row]->tpl)) {  // routed: status 1 without a device call
-      std::fill(c, c + YKPRED_AFFINITY_HEADROOM_CELLS, (int64_t)0);
-      c[3] = 1;
-    } else {
-      list.push_back(row);
-      slot.push_back(i);
-    }
-  }
-  if (list.empty() && world <= 1) return 0;
-  std::vector<int64_t> rows(list.size() * (size_t)YKPRED_AFFINITY_HEADROOM_CELLS);
-  rc = ykpred_headroom_affinity(h->eng, (int32_t)list.size(), list.data(), h->alloc_pre, h->alloc_filt, rows.data());
-  if (rc) return fail(h, std::string("ykpred_headroom_affinity: ") + ykpred_last_error(h->eng), rc);
-  for (size_t k = 0; k < list.size(); ++k)
-    memcpy(out_cells + (size_t)slot[k] * YKPRED_AFFINITY_HEADROOM_CELLS, rows.data() + k * YKPRED_AFFINITY_HEADROOM_CELLS,
-           YKPRED_AFFINITY_HEADROOM_CELLS * sizeof(int64_t));
-  return 0;
+  return headroom_list(h, "headroom_affinity", YKPRED_AFFINITY_HEADROOM_CELLS, false, [](ykhost* hh) { return upload_spec_effects(hh, true); },
+                       ykpred_headroom_affinity, n, asks, out_cells);
 }
 
 int32_t ykhost_headroom_affinity_domains(ykhost_t* h, int32_t pod, int64_t* out_summary, int64_t* out_rows, int32_t max_domains, char* values,
                                          int64_t values_len) {
   YKHOST_LOCKED(h);
   if (!out_summary || max_domains < 0 || !out_rows) return fail(h, "headroom_affinity_domains: bad argument", -1);
-  copy_out("[]", values, values_len);
-  int rc = ykhost_headroom_affinity(h, 1, &pod, out_summary);
-  if (rc) return rc;
-  if (out_summary[3] != 0 && out_summary[3] != 4) return 0;
-  int32_t D = 0;
-  rc = ykpred_headroom_affinity_pod(h->eng, pod, h->alloc_pre, h->alloc_filt, max_domains, out_rows, &D);
-  if (rc == YKPRED_E_INVALID && D > max_domains) return D;  // (the size needed, as ykhost_explain_format reports a length)
-  if (rc) return fail(h, std::string("ykpred_headroom_affinity_pod: ") + ykpred_last_error(h->eng), rc);
-  const std::vector<std::string> names = spread_domain_values(h, out_summary[12]);
-  std::string o = "[";
-  for (int32_t d = 0; d < D; ++d) {
-    if (d) o += ',';
-    js_str(o, (size_t)d < names.size() ? names[(size_t)d] : std::string());
-  }
-  o += ']';
-  copy_out(o, values, values_len);
-  return D;
+  return headroom_rows(h, "headroom_affinity", true, ykhost_headroom_affinity, ykpred_headroom_affinity_pod, pod, out_summary, out_rows,
+                       max_domains, values, values_len);
 }
 
 // One ask named as the core names it, one crossing: the summary and the domain with the most copies as a label value.
 int32_t ykhost_headroom_affinity_by_key(ykhost_t* h, const char* allocation_key, int64_t* out16, char* best, int64_t best_len) {
   YKHOST_LOCKED(h);
-  if (!out16) return fail(h, "headroom_affinity_by_key: bad argument", -1);
-  std::fill(out16, out16 + YKPRED_AFFINITY_HEADROOM_CELLS, (int64_t)0);
-  copy_out("", best, best_len);
-  ensure_uid_index(h);
-  auto it = h->by_uid.find(allocation_key ? allocation_key : "");
-  if (it == h->by_uid.end()) return YKHOST_E_POD_NOT_FOUND;
-  if (!it->second->ask) return fail(h, "pod holds no ask row", YKHOST_E_NOT_AN_ASK);
-  if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
-  int rc = sync(h);
-  if (rc) return rc;
-  auto un = h->enc.unsupported.find(it->second->tpl);
-  if (un != h->enc.unsupported.end()) {
-    out16[3] = 1;
-    return fail(h, "ask is not evaluated by the engine (route it to the CPU predicate manager): " + un->second, YKHOST_E_UNSUPPORTED);
-  }
-  const int32_t row = it->second->row;
-  rc = ykhost_headroom_affinity(h, 1, &row, out16);
-  if (rc) return rc;
-  if ((out16[3] == 0 || out16[3] == 4) && out16[11] >= 0) {
-    const std::vector<std::string> names = spread_domain_values(h, out16[12]);
-    if ((size_t)out16[11] < names.size()) copy_out(names[(size_t)out16[11]], best, best_len);
-  }
-  return 0;
+  return headroom_by_key(h, "headroom_affinity", true, ykhost_headroom_affinity, allocation_key, out16, best, best_len);
 }
-
 int32_t ykhost_pod_request_json(ykhost_t* h, int32_t pod, char* out, int32_t len) {
   YKHOST_LOCKED(h);
   if (pod < 0 || pod >= (int)h->pending.size()) return fail(h, "index out of range");

@@ -685,28 +685,33 @@ class GpuPredicateManager:
         return buf.value.decode()
 
     # ---- how many copies of an ask still fit -----------------------------------------------------------------------
-    def headroom(self, pods=None, pre_mask=None, filt_mask=None):
-        """Per ask how many copies of it the cluster can still place, reduced on the device (ykpred_headroom): np.int64[n,
-        HEADROOM_CELLS]. pods: ask indices or UIDs in any order, repeats allowed; None = every ask. Always the allocation-phase
-        lists (the reservation lists carry no NodeResourcesFit); explicit masks go to ykpred_headroom directly, like query. Needs
-        no evaluation and disturbs none. A routed ask gets [HEADROOM_STATUS] = 1, a coupled one 2 with total = max = -1."""
+    def _headroom_list(self, name, cells, pods, pre_mask, filt_mask, before_engine):
+        """What headroom, headroom_spread and headroom_affinity share: pods → indices, np.int64[n, cells], and either the host call
+        (ykhost_<name>) or, with explicit masks, before_engine() and the engine call (ykpred_<name>)."""
         if pods is None:
             count, ptr = self.num_pods, None
         else:
             idx = [p if isinstance(p, (int, np.integer)) else self.pod_index(p) for p in pods]
             arr = np.ascontiguousarray(idx, dtype=np.int32)
             count, ptr = len(arr), arr.ctypes.data
-        out = np.zeros((max(count, 1), HEADROOM_CELLS), dtype=np.int64)
+        out = np.zeros((max(count, 1), cells), dtype=np.int64)
         if pre_mask is None and filt_mask is None:
-            self._check(self._L.ykhost_headroom(self._h, count, ptr, out.ctypes.data))
+            self._check(getattr(self._L, "ykhost_" + name)(self._h, count, ptr, out.ctypes.data))
         else:
-            self.sync()
+            before_engine()
             pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
             if ptr is None:
                 arr = np.arange(count, dtype=np.int32)
                 ptr = arr.ctypes.data
-            self._pcheck(self._P.ykpred_headroom(self.engine, count, ptr, pre, filt, out.ctypes.data))
+            self._pcheck(getattr(self._P, "ykpred_" + name)(self.engine, count, ptr, pre, filt, out.ctypes.data))
         return out[:count].copy()
+
+    def headroom(self, pods=None, pre_mask=None, filt_mask=None):
+        """Per ask how many copies of it the cluster can still place, reduced on the device (ykpred_headroom): np.int64[n,
+        HEADROOM_CELLS]. pods: ask indices or UIDs in any order, repeats allowed; None = every ask. Always the allocation-phase
+        lists (the reservation lists carry no NodeResourcesFit); explicit masks go to ykpred_headroom directly, like query. Needs
+        no evaluation and disturbs none. A routed ask gets [HEADROOM_STATUS] = 1, a coupled one 2 with total = max = -1."""
+        return self._headroom_list("headroom", HEADROOM_CELLS, pods, pre_mask, filt_mask, self.sync)
 
     def headroom_nodes(self, pod, pre_mask=None, filt_mask=None):
         """How many copies of ONE ask (index or UID) each node takes (ykpred_headroom_pod): np.int32[N]; -1 everywhere for a
@@ -777,23 +782,7 @@ class GpuPredicateManager:
         np.int64[n, SPREAD_HEADROOM_CELLS]. pods: ask indices or UIDs in any order, repeats allowed; None = every ask. Allocation-phase
         lists; explicit masks go to the engine directly, like headroom. Needs no evaluation and disturbs none. [3] is the status: 0
         computed, 1 routed, 2 still coupled (total = max = -1), 3 not coupled under these lists (headroom() answers)."""
-        if pods is None:
-            count, ptr = self.num_pods, None
-        else:
-            idx = [p if isinstance(p, (int, np.integer)) else self.pod_index(p) for p in pods]
-            arr = np.ascontiguousarray(idx, dtype=np.int32)
-            count, ptr = len(arr), arr.ctypes.data
-        out = np.zeros((max(count, 1), SPREAD_HEADROOM_CELLS), dtype=np.int64)
-        if pre_mask is None and filt_mask is None:
-            self._check(self._L.ykhost_headroom_spread(self._h, count, ptr, out.ctypes.data))
-        else:
-            self.sync()
-            pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
-            if ptr is None:
-                arr = np.arange(count, dtype=np.int32)
-                ptr = arr.ctypes.data
-            self._pcheck(self._P.ykpred_headroom_spread(self.engine, count, ptr, pre, filt, out.ctypes.data))
-        return out[:count].copy()
+        return self._headroom_list("headroom_spread", SPREAD_HEADROOM_CELLS, pods, pre_mask, filt_mask, self.sync)
 
     def headroom_spread_domains(self, pod, pre_mask=None, filt_mask=None):
         """The per-domain rows behind headroom_spread for ONE ask (index or UID): (cells np.int64[SPREAD_HEADROOM_CELLS], rows
@@ -831,23 +820,9 @@ class GpuPredicateManager:
         None = every ask. Allocation-phase lists; explicit masks go to the engine directly (the spec effects must then be uploaded:
         any call with the default lists does that). Needs no evaluation and disturbs none. [3] is the status: 0 computed, 1 routed,
         2 still coupled (total = max = -1), 3 no inter-pod affinity constraint is live, 4 bootstrap (total = -1, per-domain rows valid)."""
-        if pods is None:
-            count, ptr = self.num_pods, None
-        else:
-            idx = [p if isinstance(p, (int, np.integer)) else self.pod_index(p) for p in pods]
-            arr = np.ascontiguousarray(idx, dtype=np.int32)
-            count, ptr = len(arr), arr.ctypes.data
-        out = np.zeros((max(count, 1), AFFINITY_HEADROOM_CELLS), dtype=np.int64)
-        if pre_mask is None and filt_mask is None:
-            self._check(self._L.ykhost_headroom_affinity(self._h, count, ptr, out.ctypes.data))
-        else:
-            self._check(self._L.ykhost_headroom_affinity(self._h, 0, None, None))  # (an empty list: syncs and uploads the spec effects)
-            pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
-            if ptr is None:
-                arr = np.arange(count, dtype=np.int32)
-                ptr = arr.ctypes.data
-            self._pcheck(self._P.ykpred_headroom_affinity(self.engine, count, ptr, pre, filt, out.ctypes.data))
-        return out[:count].copy()
+        # (an empty list: syncs and uploads the spec effects)
+        upload = lambda: self._check(self._L.ykhost_headroom_affinity(self._h, 0, None, None))
+        return self._headroom_list("headroom_affinity", AFFINITY_HEADROOM_CELLS, pods, pre_mask, filt_mask, upload)
 
     def headroom_affinity_domains(self, pod, pre_mask=None, filt_mask=None):
         """The per-domain rows behind headroom_affinity for ONE ask (index or UID): (cells np.int64[AFFINITY_HEADROOM_CELLS], rows
