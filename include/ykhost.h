@@ -321,6 +321,37 @@ int32_t ykhost_headroom_affinity_domains(ykhost_t* h, int32_t pod, int64_t* out_
                                          int32_t max_domains, char* values, int64_t values_len);
 int32_t ykhost_headroom_affinity_by_key(ykhost_t* h, const char* allocation_key, int64_t* out16 /* [16] */, char* best, int64_t best_len);
 
+/* PREEMPTION REACH (ykpred.h: ykpred_preempt_reach) — can preemption help an ask at all, and on which nodes? — asked before the core
+ * builds a victim list per node and walks the nodes through PreemptionPredicates. The mirror keeps what the reference's shim reads of a
+ * pod for preemption: spec.priority (0 when missing), spec.preemptionPolicy and the pod-level opt-out annotation
+ * yunikorn.apache.org/allow-preemption: "false". Always the ALLOCATION-phase plugin lists, as the reference uses for preemption.
+ *   ykhost_set_preemption_tiers  ascending priority bounds b[0] < ... < b[T-1], 1 <= T <= 8. A pod on a node is in tier t = the smallest
+ *                                t with priority < b[t]; a pod of priority >= b[T-1], an opted-out pod and a pod on no node are in no
+ *                                tier and never victims. T == 0 switches the feature off and drops the device table. Nothing is built or
+ *                                uploaded until the bounds are set. The LIMIT of an ask = the number of bounds <= its priority, 0 with
+ *                                preemptionPolicy: Never.
+ *   ykhost_preempt_reach         syncs, brings the device's reclaim table up to date — whole after a node was added or removed or the
+ *                                bounds changed, else only the columns of the nodes whose pods changed (add / remove / update / assume /
+ *                                forget) — and makes ONE engine call for the listed asks (NULL = asks 0..n-1): out_cells[i] = the
+ *                                YKPRED_REACH_CELLS cells. An ask routed to the CPU manager gets status [10] = 1 without a device call.
+ *                                YKPRED_E_STATE without tiers. Collective on a node-sharded handle: every rank passes the same asks.
+ *   ykhost_preempt_reach_nodes   the level of ONE ask on every node (ykpred_preempt_reach_pod), -1 = never: the shortlist the caller
+ *                                walks for the real victim selection; this shard's nodes on a node-sharded handle.
+ *   ykhost_preempt_reach_by_key  ONE crossing for one ask by allocation key (pod UID): the cells, and the best node ([13]) by NAME (""
+ *                                when there is none, or when it lies on another shard). → 0, or the errors of ykhost_headroom_by_key
+ *                                (YKHOST_E_UNSUPPORTED with out16[10] = 1).
+ *   ykhost_reclaim_table         the planes the mirror would upload, copied out: dims = { T, R, KP, N }; requests [T][R][N], pods [T][N],
+ *                                ports_after [T][KP][N] (any of the three may be NULL: only the dims come back). Works on a mirror-only
+ *                                handle: the table can be checked without a device. */
+int32_t ykhost_set_preemption_tiers(ykhost_t* h, const int32_t* bounds, int32_t num_tiers);
+int32_t ykhost_preempt_reach(ykhost_t* h, int32_t n, const int32_t* asks /* NULL = asks 0..n-1 */, int64_t* out_cells /* [n][16] */);
+int32_t ykhost_preempt_reach_nodes(ykhost_t* h, int32_t pod, int32_t* out /* [N] */);
+int32_t ykhost_preempt_reach_by_key(ykhost_t* h, const char* allocation_key, int64_t* out16 /* [16] */, char* best_node_name, int64_t len);
+int32_t ykhost_reclaim_table(ykhost_t* h, int32_t* dims /* [4] */, int64_t* requests, int32_t* pods, uint64_t* ports_after);
+/* The limits of the listed asks (NULL = asks 0..n-1) as the mirror derives them, after the sync and the reclaim-table update of
+ * ykhost_preempt_reach and without an engine query: what a caller of ykpred_preempt_reach with plugin lists of its own passes on. */
+int32_t ykhost_preempt_limits(ykhost_t* h, int32_t n, const int32_t* asks /* NULL = asks 0..n-1 */, int32_t* out_limits /* [n] */);
+
 /* Engine calls that came back YKPRED_E_DEVICE / YKPRED_E_NOMEM so far (failed allocation, lost device). Each one marks the whole
  * device state stale: the failing call returns its error (Predicates() < 0: the Go manager routes the ask to the CPU predicate
  * manager — SURVEY.md §5, "must degrade, never fail scheduling"), the mirror stays intact, and the next ykhost_sync /

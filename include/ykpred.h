@@ -38,7 +38,9 @@
 extern "C" {
 #endif
 
-/* (ykpred_headroom_affinity + ykpred_headroom_affinity_pod + YKPRED_AFFINITY_HEADROOM_CELLS arrived WITHIN version 4 too:
+/* (ykpred_preempt_reach + ykpred_preempt_reach_pod + ykpred_set_reclaim + ykpred_update_reclaim_node + YKPRED_REACH_CELLS arrived
+ *    WITHIN version 4 too: dlsym("ykpred_preempt_reach"))
+ * (ykpred_headroom_affinity + ykpred_headroom_affinity_pod + YKPRED_AFFINITY_HEADROOM_CELLS arrived WITHIN version 4 too:
  *    dlsym("ykpred_headroom_affinity"))
  * (ykpred_headroom_spread + ykpred_headroom_spread_pod + YKPRED_SPREAD_HEADROOM_CELLS arrived WITHIN version 4 too:
  *    dlsym("ykpred_headroom_spread"))
@@ -674,6 +676,60 @@ int32_t ykpred_preemption_batch(ykpred_engine_t* e, int32_t num_queries, const i
                                 const uint8_t* victim_present /* [total] */, const uint64_t* port_bits_after /* [total][KP] or NULL */,
                                 const int32_t* start_index /* [num_queries] */, uint32_t prefilter_plugins, uint32_t filter_plugins,
                                 int32_t* out_index /* [num_queries] */);
+
+/* PREEMPTION REACH — can preemption help an ask at all, and on which nodes? — answered before any victim list exists.
+ *
+ * The RECLAIM TABLE is resident beside the node table and shard-local on the node axis. The caller gives ascending priority bounds
+ * b[0] < ... < b[T-1], 1 <= T <= YKPRED_REACH_MAX_TIERS; a resident pod's TIER is the smallest t with priority(pod) < b[t]; a pod of
+ * priority >= b[T-1], a pod that opted out of preemption and a pod on no node are in no tier. Per tier and node the table holds what
+ * the node's pods of that tier give back: */
+#define YKPRED_REACH_MAX_TIERS 8
+typedef struct ykpred_reclaim {
+  int32_t tiers;               /* T */
+  const int64_t* requests;     /* [T][R][N] summed request vectors per tier, not cumulative */
+  const int32_t* pods;         /* [T][N] pods of the tier on the node */
+  const uint64_t* ports_after; /* [T][KP][N] the node's port_bits once tiers 0..t are gone; NULL = no victim holds a dictionary port
+                                  or KP == 0 */
+} ykpred_reclaim_t;
+/* Uploads the table for the current node table (YKPRED_E_STATE without one). NULL drops it. A ykpred_set_nodes that changes N drops it
+ * as well. No other call reads the table, and setting it invalidates no evaluation. */
+int32_t ykpred_set_reclaim(ykpred_engine_t* e, const ykpred_reclaim_t* table);
+/* One column of every plane, in the style of ykpred_update_node: `one` describes ONE node (N == 1 in the shapes above) with the
+ * resident table's tier count. ports_after must be given exactly when the resident table has that plane. */
+int32_t ykpred_update_reclaim_node(ykpred_engine_t* e, int32_t node_index, const ykpred_reclaim_t* one);
+
+/* level(a, n): 0 when Predicates(a, n) fits as the node stands; otherwise the smallest L <= limit such that the ask fits once ALL pods
+ * of tiers < L are gone from n — free resources grow by the tier's request vector, len(Pods) drops by its pod count, the port words
+ * become ports_after, the PreFilter state of PodTopologySpread / InterPodAffinity stays frozen: ykpred_preemption's removal with whole
+ * tiers as steps; NEVER when no such L exists or a PreFilter plugin rejects the pair. With victims = the node's pods of tiers < limit
+ * in ascending tier order, level == tier(victims[i]) + 1 for i = ykpred_preemption(a, n, victims, start 0), and i == -1 <=> never.
+ * The limit of an ask = the number of bounds <= its priority (0 for preemptionPolicy: Never): the caller passes it. */
+#define YKPRED_REACH_CELLS 16
+/* per ask, int64[16], over all nodes of the table:
+ *  [0]      nodes at level 0 (== bin [9] of ykpred_explain)
+ *  [1..8]   nodes at level 1..8
+ *  [9]      nodes never
+ *  [10]     status: 0 computed; 1 the ask's spec is YKPRED_SPEC_UNSUPPORTED (every other cell 0 except [11])
+ *  [11]     the limit, echoed
+ *  [12]     the lowest level >= 1 that has a node, or 0
+ *  [13]     the BEST node at that level: the fewest pods in tiers < level, ties to the lowest node index (a GLOBAL index on a sharded
+ *           engine); -1 when there is none
+ *  [14]     that node's pod count in those tiers (saturating at 2^28 - 1)
+ *  [15]     0
+ * Invariant at status 0: [0] + ... + [9] == N.
+ * Everything else is ykpred_explain's: the listed asks are reduced to their distinct (spec, NodeName, limit) tasks; the call reads the
+ *   TABLES only, needs no evaluation and invalidates none; it prepares the topology histograms as ykpred_query does; it counts as one
+ *   query; roctx range "ykpred:preempt_reach"; the same errors, plus YKPRED_E_STATE without a reclaim table and YKPRED_E_INVALID for a
+ *   limit outside 0..T.
+ * NODE-SHARDED engines: COLLECTIVE like ykpred_explain — the agreement all-gather first (it covers the limits), then one all-reduce SUM
+ *   (int64) of the cells and one all-reduce MIN (int64) of the packed best keys: every rank returns CLUSTER-WIDE cells. */
+int32_t ykpred_preempt_reach(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks /* host, ask indices, any order, repeats allowed */,
+                             const int32_t* limits /* host, [n_asks], 0..T */, uint32_t prefilter_plugins, uint32_t filter_plugins,
+                             int64_t* out /* host, [n_asks][YKPRED_REACH_CELLS] */);
+/* level(pod, n) for every node n of the table (thread = node, as ykpred_headroom_pod), -1 = never: the shortlist the caller walks for
+ * the real victim selection. -1 everywhere for a YKPRED_SPEC_UNSUPPORTED spec. This shard's nodes only on a sharded engine. */
+int32_t ykpred_preempt_reach_pod(ykpred_engine_t* e, int32_t pod_index, int32_t limit, uint32_t prefilter_plugins, uint32_t filter_plugins,
+                                 int32_t* out /* [N] */);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Multi-GPU: node-axis shards. One engine per GPU / process holds a contiguous shard of the node table and

@@ -592,6 +592,57 @@ func (m *gpuPredicateManager) AffinityHeadroom(pod *v1.Pod) (total, domains, mos
 	}
 }
 
+// SetPreemptionTiers hands the engine the ascending priority bounds that cut the resident pods into tiers (at most 8); an empty slice
+// switches PreemptionReach off. The bounds are the priorities of the cluster's PriorityClasses, or a coarser cut of them.
+func (m *gpuPredicateManager) SetPreemptionTiers(bounds []int32) error {
+	var first *C.int32_t
+	if len(bounds) > 0 {
+		first = (*C.int32_t)(unsafe.Pointer(&bounds[0]))
+	}
+	if rc := C.ykhost_set_preemption_tiers(m.host, first, C.int32_t(len(bounds))); rc != 0 {
+		return errors.New(C.GoString(C.ykhost_last_error(m.host)))
+	}
+	return nil
+}
+
+// PreemptionReach answers, before any victim list exists, whether preemption can help the ask at all and where: how many nodes take the
+// ask as they stand, how many only once lower-priority pods are gone, how many never — shut by a taint, a selector or a frozen topology
+// verdict that no eviction cures — and the node that needs the fewest victims at the lowest tier. The call site is in front of the node
+// walk that ends in IsPodFitNodeViaPreemption (context.go:718-742): with reachable == 0 the walk is skipped, otherwise it starts at
+// bestNode. ONE crossing: ykhost_preempt_reach_by_key looks the ask up by allocation key and hands the node back by name. ok == false
+// when the pod is not a mirrored ask, is routed to the CPU predicate manager, no tiers are set or the engine failed: the caller walks
+// every node as before.
+func (m *gpuPredicateManager) PreemptionReach(pod *v1.Pod) (fits, reachable, never int64, bestLevel int, bestNode string, bestVictims int64, ok bool) {
+	if pod == nil {
+		return 0, 0, 0, 0, "", 0, false
+	}
+	var cells [16]C.int64_t
+	var best [256]C.char
+	uid := C.CString(string(pod.UID))
+	rc := C.ykhost_preempt_reach_by_key(m.host, uid, &cells[0], &best[0], 256)
+	C.free(unsafe.Pointer(uid))
+	switch {
+	case rc == 0 && cells[10] == 0:
+		for level := 1; level <= 8; level++ {
+			reachable += int64(cells[level])
+		}
+		return int64(cells[0]), reachable, int64(cells[9]), int(cells[12]), C.GoString(&best[0]), int64(cells[14]), true
+	case rc == 0:
+		return 0, 0, 0, 0, "", 0, false
+	case rc == C.YKHOST_E_UNSUPPORTED:
+		m.Counters.RoutedUnsupported.Add(1)
+		return 0, 0, 0, 0, "", 0, false
+	case rc == C.YKHOST_E_POD_NOT_FOUND || rc == C.YKHOST_E_NOT_AN_ASK:
+		m.Counters.RoutedNotMirrored.Add(1)
+		return 0, 0, 0, 0, "", 0, false
+	default:
+		m.Counters.RoutedOnError.Add(1)
+		log.Log(log.ShimPredicates).Warn("GPU predicate engine error, no preemption reach for the ask",
+			zap.String("error", C.GoString(C.ykhost_last_error(m.host))))
+		return 0, 0, 0, 0, "", 0, false
+	}
+}
+
 // ResidentStats: Predicates() calls answered from the mirrored resident answer, per pair because the node's column changed,
 // by whole-ask device queries, and the answer / failing-plugin fetches behind them.
 func (m *gpuPredicateManager) ResidentStats() (resident, dirtyColumn, query, answerFetches, codeFetches int64) {

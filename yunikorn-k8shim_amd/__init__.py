@@ -9,6 +9,7 @@ from .predicate_manager import (ALL_PLUGINS, EXPLAIN_BINS, EXPLAIN_FIT, EXPLAIN_
                                 EXPLAIN_UNSUPPORTED, GROUP_CELLS, GROUP_LDS_MAX_GROUPS, GROUP_SUMMARY, HEADROOM_BY_PORT, HEADROOM_BY_RESOURCE0, HEADROOM_BY_SLOTS, HEADROOM_CELLS,
                                 HEADROOM_MAX, HEADROOM_NODES, HEADROOM_STATUS, HEADROOM_TOTAL, PLUGIN_BITS, SPREAD_HEADROOM_CELLS, SPREAD_ROW_CELLS,
                                 AFFINITY_HEADROOM_CELLS,
+                                REACH_BEST_LEVEL, REACH_BEST_NODE, REACH_BEST_PODS, REACH_CELLS, REACH_LIMIT, REACH_MAX_TIERS, REACH_NEVER, REACH_STATUS,
                                 GpuPredicateManager,
                                 PredicateError, UnsupportedAsk, plugin_mask)
 

@@ -46,6 +46,10 @@ class YkpredLayout(C.Structure):
                 ("sweep_rows", C.c_int32), ("index_rows_walked", C.c_int32), ("run_rows", C.c_int32), ("fused_rows", C.c_int32)]
 
 
+class YkpredReclaim(C.Structure):
+    _fields_ = [("tiers", C.c_int32), ("requests", C.c_void_p), ("pods", C.c_void_p), ("ports_after", C.c_void_p)]
+
+
 MAX_TIMED = 24
 
 
@@ -145,6 +149,10 @@ def load_ykpred():
     L.ykpred_headroom_affinity.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     L.ykpred_headroom_affinity_pod.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p]
     L.ykpred_headroom_affinity_constraint.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.ykpred_set_reclaim.argtypes = [C.c_void_p, C.POINTER(YkpredReclaim)]
+    L.ykpred_update_reclaim_node.argtypes = [C.c_void_p, C.c_int32, C.POINTER(YkpredReclaim)]
+    L.ykpred_preempt_reach.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.ykpred_preempt_reach_pod.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
     _pred = L
     return L
 
@@ -232,6 +240,12 @@ def load_ykhost():
     L.ykhost_headroom_affinity.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.ykhost_headroom_affinity_domains.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_char_p, C.c_int64]
     L.ykhost_headroom_affinity_by_key.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_char_p, C.c_int64]
+    L.ykhost_set_preemption_tiers.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+    L.ykhost_preempt_reach.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.ykhost_preempt_reach_nodes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    L.ykhost_preempt_reach_by_key.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_char_p, C.c_int64]
+    L.ykhost_preempt_limits.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.ykhost_reclaim_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ykhost_device_errors.restype = C.c_int64
     L.ykhost_device_errors.argtypes = [C.c_void_p]
     _host = L

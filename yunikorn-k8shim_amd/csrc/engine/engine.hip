@@ -278,6 +278,11 @@ struct ykpred_engine {
   DevBuf d_headroom;  // ykpred_headroom: [tasks][YKPRED_HEADROOM_CELLS] cells | [tasks] max replicas | task specs | task pins
   DevBuf d_groups;  // ykpred_headroom_groups: summaries | pair wants | pair tasks | task specs | task pins | coupled | node groups | one table chunk
   DevBuf d_domain_head;  // headroom_domains_run (ykpred_headroom_spread, _affinity): summaries | tasks | one table chunk (rows | extra cells)
+  DevBuf d_reach;  // ykpred_preempt_reach: [tasks][YKPRED_REACH_CELLS] cells | [tasks] best keys | task specs | task pins | task limits
+  // the resident reclaim table (ykpred_set_reclaim): what the pods of each priority tier give back per node
+  DevBuf d_rc_req, d_rc_pods, d_rc_ports;  // [T][R][N] i64; [T][N] int; [T][KP][N] u64 (only with rc_ports)
+  int rc_tiers = 0;                        // 0 = no table
+  bool rc_ports = false;
   DevBuf d_bytes_gather;  // ykpred_comm_allgather_bytes
   DevBuf d_topo_agree;  // node-sharded: the shape of every rank's topology histograms (agree_topology)
   u64 dict_digest = 0;  // ykpred_set_dictionary_digest
@@ -1775,7 +1780,7 @@ void ykpred_destroy(ykpred_engine_t* e) {
                     &e->d_member_key, &e->d_name_rank, &e->d_member_tie, &e->d_class_rows_all, &e->d_gathered_classes, &e->d_class_rows_slot,
                     &e->d_class_sig_ident, &e->d_expand_count, &e->d_layout_hash, &e->d_gathered_pod_class, &e->d_row_pod,
                     &e->d_round, &e->d_fx_off, &e->d_fx_cls, &e->d_fx_cnt, &e->d_fx_occ, &e->d_sp_sig_of, &e->d_class_list_b, &e->d_gathered, &e->d_gathered_map,
-                    &e->d_xkey, &e->d_xcand})
+                    &e->d_xkey, &e->d_xcand, &e->d_reach, &e->d_rc_req, &e->d_rc_pods, &e->d_rc_ports})
     b->release();
   if (e->ev_ready)
     for (auto& ev : e->ev) (void)hipEventDestroy(ev);
@@ -1843,6 +1848,7 @@ int32_t ykpred_set_nodes(ykpred_engine_t* e, const ykpred_nodes_t* n) {
     e->planes_ranked.release();
     e->base_canon.release();
     e->base_ranked.release();
+    e->rc_tiers = 0;  // the reclaim table describes N nodes
   }
   e->N = n->count;
   e->row_words = (e->N + 63) / 64;
@@ -4566,6 +4572,11 @@ static u64 tune_hash(std::initializer_list<u64> words, u64 h = 0x9e3779b97f4a7c1
 extern "C++" {  // (a template: the surrounding block has C linkage)
 struct HeadroomTasks {
   std::vector<int32_t> task_of, spec, pin;  // ask i of the list → its task; per task the spec and the NodeName pin
+  const int32_t* extra = nullptr;           // [n_asks] or null: a small per-ask value (0..15) that is part of the task key ...
+  std::vector<int32_t> extra_of;            // ... and then its value per task (ykpred_preempt_reach: the limit)
+  bool need_fit = true;                     // NodeResourcesFit must be in both lists (the headroom calls: nothing else bounds the count)
+  // what a rank names as the cause when ANOTHER rank could not run the call (it knows the status, not the text)
+  const char* other_causes = "bad argument, NodeResourcesFit missing from a list, tables not uploaded, an index out of range or stale topology histograms";
 };
 // `more_checks` (a callable) runs after the common checks passed and returns a status of the call's own with its text; `more` is a
 // hash of whatever else the ranks of a sharded engine must hold alike. *run == false on return: the caller returns the status at once
@@ -4578,8 +4589,9 @@ static int32_t headroom_prepare(ykpred_engine* e, const std::string& name, int32
   int rc = YKPRED_OK;
   std::string why;
   if (n_asks < 0 || !pointers_ok) rc = YKPRED_E_INVALID, why = name + ": bad argument";
-  else if (!(pre & filt & YKPRED_PLUGIN_NODE_RESOURCES_FIT)) rc = YKPRED_E_INVALID, why = name + ": NodeResourcesFit must be in both plugin lists (nothing else bounds the count)";
+  else if (tasks->need_fit && !(pre & filt & YKPRED_PLUGIN_NODE_RESOURCES_FIT)) rc = YKPRED_E_INVALID, why = name + ": NodeResourcesFit must be in both plugin lists (nothing else bounds the count)";
   else if (!e->nodes_set || !e->specs_set || !e->pods_set) rc = YKPRED_E_STATE, why = name + ": tables not uploaded";
+  else if (tasks->extra && e->S >= (1 << 27)) rc = YKPRED_E_UNSUPPORTED, why = name + ": more than 2^27 specs";
   else
     for (int i = 0; i < n_asks; ++i)
       if (asks[i] < 0 || asks[i] >= e->P) rc = YKPRED_E_INVALID, why = name + ": index out of range";
@@ -4589,19 +4601,23 @@ static int32_t headroom_prepare(ykpred_engine* e, const std::string& name, int32
   // Tasks: the distinct (spec, pin) of the list, keyed as ykpred_explain keys them (a sharded engine cannot key on the pin, a node index
   // of ITS shard; with by_ask every distinct ask index is a task — the keys every rank derives alike).
   std::vector<int32_t>&task_of = tasks->task_of, &t_spec = tasks->spec, &t_pin = tasks->pin;
+  const int32_t* extra = tasks->extra;
   auto build_tasks = [&](bool by_ask) {
     std::unordered_map<u64, int32_t> index;
     task_of.assign((size_t)n_asks, 0);
     t_spec.clear();
     t_pin.clear();
+    tasks->extra_of.clear();
     for (int i = 0; i < n_asks; ++i) {
       const int32_t a = asks[i], sp = e->h_pod_spec[(size_t)a], pin = e->h_pod_pin[(size_t)a];
       u64 key = ((u64)(uint32_t)sp << 32) | (u64)(uint32_t)pin;
       if (by_ask || (sharded && pin != YKPRED_NO_NODE_NAME)) key = (1ull << 63) | (u64)(uint32_t)a;
+      if (extra) key |= (u64)(extra[i] & 15) << 59;  // (bits 59..62: free under 2^27 specs, and above an ask index)
       auto it = index.emplace(key, (int32_t)t_spec.size());
       if (it.second) {
         t_spec.push_back(sp);
         t_pin.push_back(pin);
+        if (extra) tasks->extra_of.push_back(extra[i]);
       }
       task_of[(size_t)i] = it.first->second;
     }
@@ -4639,7 +4655,7 @@ static int32_t headroom_prepare(ykpred_engine* e, const std::string& name, int32
     for (int g = 0; g < W; ++g)
       if (all[(size_t)g].rc != YKPRED_OK)
         return fail(e, all[(size_t)g].rc, name + " (sharded): rank " + std::to_string(g) + " cannot run the call (" +
-                                              (g == e->comm_rank && !why.empty() ? why : "bad argument, NodeResourcesFit missing from a list, tables not uploaded, an index out of range or stale topology histograms") +
+                                              (g == e->comm_rank && !why.empty() ? why : tasks->other_causes) +
                                               "): no rank runs it");
     for (int g = 0; g < W; ++g)
       if (all[(size_t)g].n != all[0].n || all[(size_t)g].list != all[0].list)
@@ -4736,6 +4752,169 @@ int32_t ykpred_headroom_pod(ykpred_engine_t* e, int32_t pod, uint32_t pre, uint3
   HIPCHK(e->d_scratch.ensure(N * sizeof(int32_t) + 64));
   hipLaunchKernelGGL(ykk::k_headroom_pod, dim3((unsigned)((N + ykk::kBlock - 1) / ykk::kBlock)), dim3(ykk::kBlock), 0, st, node_table(e),
                      spec_table(e), spec, e->h_pod_pin[(size_t)pod], pre, filt, e->d_scratch.as<int32_t>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, e->d_scratch.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return YKPRED_OK;
+}
+
+// The resident reclaim table of ykpred_preempt_reach: three planes beside the node table, shard-local on the node axis. Nothing else reads
+// them, so neither call touches the evaluation state (tables_version, the epochs, the resident answer).
+int32_t ykpred_set_reclaim(ykpred_engine_t* e, const ykpred_reclaim_t* rt) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:upload_reclaim");
+  if (!e) return YKPRED_E_INVALID;
+  e->n_uploads++;
+  if (!rt) {
+    e->rc_tiers = 0;
+    return YKPRED_OK;
+  }
+  if (!e->nodes_set) return fail(e, YKPRED_E_STATE, "set_reclaim: no node table");
+  if (rt->tiers < 1 || rt->tiers > YKPRED_REACH_MAX_TIERS) return fail(e, YKPRED_E_INVALID, "set_reclaim: tiers must be 1 .. 8");
+  if (e->N > 0 && (!rt->requests || !rt->pods)) return fail(e, YKPRED_E_INVALID, "set_reclaim: null plane");
+  HIPCHK(hipSetDevice(e->cfg.device));
+  hipStream_t st = e->own_stream;
+  const size_t N = (size_t)e->N, T = (size_t)rt->tiers;
+  e->rc_tiers = 0;
+  TRY(upload(e, e->d_rc_req, rt->requests, T * (size_t)e->R * N, st));
+  TRY(upload(e, e->d_rc_pods, rt->pods, T * N, st));
+  const bool ports = rt->ports_after && e->KP > 0;
+  if (ports) TRY(upload(e, e->d_rc_ports, rt->ports_after, T * (size_t)e->KP * N, st));
+  HIPCHK(hipStreamSynchronize(st));
+  e->rc_ports = ports;
+  e->rc_tiers = rt->tiers;
+  return YKPRED_OK;
+}
+
+int32_t ykpred_update_reclaim_node(ykpred_engine_t* e, int32_t idx, const ykpred_reclaim_t* one) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:update_reclaim_node");
+  if (!e || !one || !one->requests || !one->pods) return fail(e, YKPRED_E_INVALID, "update_reclaim_node: bad argument");
+  e->n_uploads++;
+  if (!e->nodes_set || e->rc_tiers == 0) return fail(e, YKPRED_E_STATE, "update_reclaim_node: no reclaim table");
+  if (idx < 0 || idx >= e->N) return fail(e, YKPRED_E_INVALID, "update_reclaim_node: index out of range");
+  if (one->tiers != e->rc_tiers) return fail(e, YKPRED_E_INVALID, "update_reclaim_node: tier count differs from the resident table");
+  if (e->rc_ports != (one->ports_after != nullptr && e->KP > 0))
+    return fail(e, YKPRED_E_INVALID, "update_reclaim_node: ports_after must be given exactly when the resident table has the plane — re-upload the table");
+  HIPCHK(hipSetDevice(e->cfg.device));
+  hipStream_t st = e->own_stream;
+  const size_t N = (size_t)e->N;
+  for (int t = 0; t < e->rc_tiers; ++t) {
+    for (int r = 0; r < e->R; ++r)
+      HIPCHK(hipMemcpyAsync(e->d_rc_req.as<i64>() + ((size_t)t * e->R + r) * N + idx, one->requests + (size_t)t * e->R + r, sizeof(i64), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->d_rc_pods.as<int>() + (size_t)t * N + idx, one->pods + t, sizeof(int), hipMemcpyHostToDevice, st));
+    if (e->rc_ports)
+      for (int k = 0; k < e->KP; ++k)
+        HIPCHK(hipMemcpyAsync(e->d_rc_ports.as<u64>() + ((size_t)t * e->KP + k) * N + idx, one->ports_after + (size_t)t * e->KP + k, sizeof(u64), hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  return YKPRED_OK;
+}
+
+static ykk::ReclaimTable reclaim_table(ykpred_engine* e) {
+  ykk::ReclaimTable rc;
+  rc.T = e->rc_tiers;
+  rc.req = e->d_rc_req.as<ykk::i64>();
+  rc.pods = e->d_rc_pods.as<int>();
+  rc.ports_after = e->rc_ports ? e->d_rc_ports.as<ykk::u64>() : nullptr;
+  return rc;
+}
+
+// Which nodes removing lower-priority pods opens: per listed (ask, limit) the level of every node reduced on the device (k_preempt_reach).
+// The shape of ykpred_headroom — tasks, agreement, a SUM reduce — with a MIN of packed best-node keys beside it.
+int32_t ykpred_preempt_reach(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, const int32_t* limits, uint32_t pre, uint32_t filt, int64_t* out) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:preempt_reach");
+  if (e) e->n_queries++;
+  static_assert(ykk::kReachCells == YKPRED_REACH_CELLS && ykk::kReachMaxTiers == YKPRED_REACH_MAX_TIERS, "k_preempt_reach writes the layout of ykpred.h");
+  constexpr size_t B = YKPRED_REACH_CELLS;
+  if (!e) return YKPRED_E_INVALID;
+  const bool args_ok = n_asks <= 0 || (asks && limits && out);
+  auto more_checks = [&](std::string* why) -> int {
+    if (e->rc_tiers == 0) return *why = "preempt_reach: no reclaim table (ykpred_set_reclaim)", YKPRED_E_STATE;
+    for (int i = 0; i < n_asks; ++i)
+      if (limits[i] < 0 || limits[i] > e->rc_tiers) return *why = "preempt_reach: limit outside 0 .. tiers", YKPRED_E_INVALID;
+    return YKPRED_OK;
+  };
+  u64 more = tune_hash({(u64)(uint32_t)e->rc_tiers});
+  if (n_asks > 0 && args_ok)
+    for (int i = 0; i < n_asks; ++i) more = tune_hash({(u64)(uint32_t)limits[i]}, more);
+  HeadroomTasks tasks;
+  tasks.extra = args_ok && n_asks > 0 ? limits : nullptr;
+  tasks.need_fit = false;
+  tasks.other_causes = "bad argument, no reclaim table, a limit outside 0 .. tiers, tables not uploaded, an index out of range or stale topology histograms";
+  bool run = false;
+  const int32_t rc = headroom_prepare(e, "preempt_reach", n_asks, asks, args_ok, pre, filt, more_checks, more, &tasks, &run);
+  if (!run) return rc;
+  const bool sharded = e->comm && e->comm_world > 1;
+  const std::vector<int32_t>&task_of = tasks.task_of, &t_spec = tasks.spec, &t_pin = tasks.pin, &t_limit = tasks.extra_of;
+  hipStream_t st = e->own_stream;
+  const size_t T = t_spec.size();
+  HIPCHK(e->d_reach.ensure(T * ((B + 1) * sizeof(int64_t) + 3 * sizeof(int32_t)) + 64));
+  int64_t* d_cells = e->d_reach.as<int64_t>();  // (the table and the keys first: what the reduces and the copy move)
+  int64_t* d_best = d_cells + T * B;
+  int32_t* d_spec = (int32_t*)(d_best + T);
+  int32_t* d_pin = d_spec + T;
+  int32_t* d_limit = d_pin + T;
+  HIPCHK(hipMemsetAsync(d_cells, 0, T * B * sizeof(int64_t), st));
+  HIPCHK(hipMemsetAsync(d_best, 0x7f, T * sizeof(int64_t), st));  // (level field 15: no node)
+  if (e->N > 0) {
+    HIPCHK(hipMemcpyAsync(d_spec, t_spec.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_pin, t_pin.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_limit, t_limit.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    const dim3 grid((unsigned)((T + ykk::kExplainTasks - 1) / ykk::kExplainTasks), (unsigned)((e->N + ykk::kBlock - 1) / ykk::kBlock));
+    hipLaunchKernelGGL(ykk::k_preempt_reach, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e), reclaim_table(e), (int)T, d_spec, d_pin,
+                       d_limit, sharded ? e->node_offset : 0, pre, filt, (ykk::i64*)d_cells, (ykk::u64*)d_best);
+    HIPCHK(hipGetLastError());
+  }
+  if (sharded) {
+    NCCLCHK(rccl()->AllReduce(d_cells, d_cells, T * B, ncclInt64, ncclSum, e->comm, st));
+    NCCLCHK(rccl()->AllReduce(d_best, d_best, T, ncclInt64, ncclMin, e->comm, st));
+  }
+  std::vector<int64_t> rows(T * (B + 1));
+  HIPCHK(hipMemcpyAsync(rows.data(), d_cells, T * (B + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  // The status per task, decided here: [10] arrives as the number of shards whose spec table does not evaluate the spec.
+  for (size_t k = 0; k < T; ++k) {
+    int64_t* row = rows.data() + k * B;
+    const u64 key = (u64)rows[T * B + k];
+    const int64_t level = (int64_t)(key >> ykk::kReachLevelShift);
+    if (row[10] != 0) {
+      std::fill(row, row + B, (int64_t)0);
+      row[10] = 1;
+      row[13] = -1;
+    } else if (level >= 1 && level <= YKPRED_REACH_MAX_TIERS) {
+      row[12] = level;
+      row[13] = (int64_t)(key & 0x7fffffffull);
+      row[14] = (int64_t)((key >> ykk::kReachPodsShift) & (u64)ykk::kReachPodsMax);
+    } else {
+      row[13] = -1;
+    }
+    row[11] = t_limit[k];
+  }
+  for (int i = 0; i < n_asks; ++i) memcpy(out + (size_t)i * B, rows.data() + (size_t)task_of[(size_t)i] * B, B * sizeof(int64_t));
+  return YKPRED_OK;
+}
+
+// the level of one ask on every node of this table (this shard's nodes on a sharded engine; nothing is exchanged)
+int32_t ykpred_preempt_reach_pod(ykpred_engine_t* e, int32_t pod, int32_t limit, uint32_t pre, uint32_t filt, int32_t* out) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:preempt_reach_pod");
+  if (e) e->n_queries++;
+  if (!e || !out) return fail(e, YKPRED_E_INVALID, "preempt_reach_pod: bad argument");
+  if (!e->nodes_set || !e->specs_set || !e->pods_set) return fail(e, YKPRED_E_STATE, "preempt_reach_pod: tables not uploaded");
+  if (e->rc_tiers == 0) return fail(e, YKPRED_E_STATE, "preempt_reach_pod: no reclaim table (ykpred_set_reclaim)");
+  if (pod < 0 || pod >= e->P) return fail(e, YKPRED_E_INVALID, "preempt_reach_pod: index out of range");
+  if (limit < 0 || limit > e->rc_tiers) return fail(e, YKPRED_E_INVALID, "preempt_reach_pod: limit outside 0 .. tiers");
+  if (e->N == 0) return YKPRED_OK;
+  HIPCHK(hipSetDevice(e->cfg.device));
+  hipStream_t st = e->own_stream;
+  if ((pre & filt & (YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD | YKPRED_PLUGIN_INTER_POD_AFFINITY))) TRY(ensure_histograms(e, st));
+  else if (e->spread_dirty) TRY(build_spread_tables(e, st));
+  const size_t N = (size_t)e->N;
+  HIPCHK(e->d_scratch.ensure(N * sizeof(int32_t) + 64));
+  hipLaunchKernelGGL(ykk::k_preempt_reach_pod, dim3((unsigned)((N + ykk::kBlock - 1) / ykk::kBlock)), dim3(ykk::kBlock), 0, st, node_table(e),
+                     spec_table(e), reclaim_table(e), e->h_pod_spec[(size_t)pod], e->h_pod_pin[(size_t)pod], limit, pre, filt, e->d_scratch.as<int32_t>());
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, e->d_scratch.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));

@@ -3707,6 +3707,129 @@ __global__ __launch_bounds__(kWave) void k_preempt(NodeTable t, SpecTable s, int
                        ports_after ? ports_after + (size_t)v0 * t.KP : nullptr, q_start[q], pre_mask, filt_mask);
 }
 
+// ykpred_preempt_reach: which nodes removing lower-priority pods opens. The resident RECLAIM TABLE holds, per priority tier and node, what
+// the node's pods of that tier give back: their summed request vector, their number, and the node's host-port words once tiers 0..t are
+// gone. reach_level is preempt_one with WHOLE TIERS as steps: 0 when the pair fits as the node stands, else the smallest L <= limit such
+// that it fits with tiers < L gone, else kReachNever; *victims = the node's pods in tiers < L. The node's registers are left as they
+// were (the walk works on a copy of the free values, the port words and the slot flag). No array is indexed by the tier: the tier's
+// columns come from global memory.
+struct ReclaimTable {
+  int T;
+  const i64* req;          // [T][R][n] per tier, not cumulative
+  const int* pods;         // [T][n]
+  const u64* ports_after;  // [T][KP][n], null: no victim holds a dictionary port
+};
+constexpr int kReachCells = 16;
+constexpr int kReachMaxTiers = 8;
+constexpr int kReachNever = kReachMaxTiers + 1;
+// The best-node key, one 64-bit MIN: level (4 bits, 1..8) | victim pods (28 bits, saturating) | global node index (31 bits). Bit 63 stays
+// clear, so the order is the same signed and unsigned (the all-reduce of a sharded engine is a signed MIN). The host fills the array
+// with bytes of 0x7f: a key whose level field is above kReachMaxTiers says "no node".
+constexpr int kReachLevelShift = 59, kReachPodsShift = 31;
+constexpr i64 kReachPodsMax = (1ll << 28) - 1;
+__device__ __forceinline__ int reach_level(const NodeTable& t, const SpecTable& s, const ReclaimTable& rc, int spec, int pin, int node,
+                                           const NodeRegs& nr, i64 count, i64 allowed, int limit, unsigned pre_mask, unsigned filt_mask,
+                                           i64* victims) {
+  int code = 0;
+  unsigned reason = 0;
+  *victims = 0;
+  if (eval_pair(s, spec, pin, node, nr, pre_mask, filt_mask, &code, &reason)) return 0;
+  // Only NodePorts (5) and NodeResourcesFit (6) read what a removed pod changes; the plugins in front of them do not move and the ones
+  // behind them are frozen, so a first failure anywhere else stays the first failure. (The walk below gives the same answer.) A
+  // PreFilter rejection is among them: eval_pair runs the PreFilter pass in front of every Filter, so a first failure at 5 or 6 says
+  // that it passed — preempt_one's separate PreFilter-only evaluation has nothing left to find here.
+  if (code != 5 && code != 6) return kReachNever;
+  NodeRegs w = nr;
+  i64 gone = 0;
+  for (int tier = 0; tier < limit; ++tier) {
+    const int np = rc.pods[(size_t)tier * t.n + node];
+    if (np == 0) continue;  // nothing leaves: the verdict of the step before stands
+#pragma unroll
+    for (int r = 0; r < kMaxR; ++r)
+      if (r < t.R) w.fr[r] += rc.req[((size_t)tier * t.R + r) * t.n + node];
+    if (rc.ports_after) {
+#pragma unroll
+      for (int k = 0; k < kMaxKP; ++k)
+        if (k < t.KP) w.pt[k] = rc.ports_after[((size_t)tier * t.KP + k) * t.n + node];
+    }
+    gone += np;
+    w.slots_ok = count - gone + 1 <= allowed;
+    if (eval_pair(s, spec, pin, node, w, pre_mask, filt_mask, &code, &reason)) {
+      *victims = gone;
+      return tier + 1;
+    }
+  }
+  return kReachNever;
+}
+
+// Grid of k_explain: blockIdx.x = chunk of kExplainTasks tasks (spec, pin, limit), blockIdx.y = 256 nodes, lane = node; the node columns
+// are loaded once per chunk. Per task the level counts are ballot popcounts (lane c keeps cell c: [0] level 0, [1..8] level 1..8, [9]
+// never), the wave's best key a wave minimum; the block's waves meet in LDS; then one global integer add per non-zero cell of
+// cells[tasks][16] and one 64-bit MIN per task that has a node at a level >= 1 into best[tasks]. Cell [10] is the `unsupported` flag.
+__global__ __launch_bounds__(kBlock) void k_preempt_reach(NodeTable t, SpecTable s, ReclaimTable rc, int n_tasks,
+                                                          const int* __restrict__ task_spec, const int* __restrict__ task_pin,
+                                                          const int* __restrict__ task_limit, int node_offset, unsigned pre_mask,
+                                                          unsigned filt_mask, i64* __restrict__ cells, u64* __restrict__ best) {
+  __shared__ int acc[kExplainTasks * kReachCells];
+  __shared__ u64 accbest[kExplainTasks];
+  for (int i = threadIdx.x; i < kExplainTasks * kReachCells; i += kBlock) acc[i] = 0;
+  if (threadIdx.x < kExplainTasks) accbest[threadIdx.x] = ~0ull;
+  __syncthreads();
+  const int lane = threadIdx.x % kWave;
+  bool live;
+  const int n = headroom_node(t, &live);
+  const int k0 = blockIdx.x * kExplainTasks, kend = min(k0 + kExplainTasks, n_tasks);
+  if (__ballot(live)) {  // (wave-uniform: a wave wholly past N skips the walk, not the barriers)
+    NodeRegs nr;
+    load_node(t, n, &nr);
+    const i64 count = live ? (i64)t.count[n] : 0, allowed = live ? (i64)t.allowed[n] : 0;
+    for (int k = k0; k < kend; ++k) {
+      i64 victims = 0;
+      const int level = live ? reach_level(t, s, rc, task_spec[k], task_pin[k], n, nr, count, allowed, task_limit[k], pre_mask, filt_mask, &victims) : -1;
+      int mine = 0;
+#pragma unroll
+      for (int c = 0; c <= kReachNever; ++c) {
+        const int v = __popcll(__ballot(level == c));
+        if (lane == c) mine = v;
+      }
+      if (lane <= kReachNever && mine) atomicAdd(&acc[(k - k0) * kReachCells + lane], mine);
+      if (__ballot(level >= 1 && level <= kReachMaxTiers)) {
+        u64 key = ~0ull;
+        if (level >= 1 && level <= kReachMaxTiers)
+          key = ((u64)level << kReachLevelShift) | ((u64)min(victims, kReachPodsMax) << kReachPodsShift) | (u64)(unsigned)(node_offset + n);
+#pragma unroll
+        for (int off = kWave / 2; off > 0; off >>= 1) {
+          const u64 o = (u64)__shfl_xor((unsigned long long)key, off, kWave);
+          key = o < key ? o : key;
+        }
+        if (lane == 0) atomicMin((unsigned long long*)&accbest[k - k0], (unsigned long long)key);
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < (kend - k0) * kReachCells; i += kBlock) {
+    const int v = acc[i];
+    if (v) atomicAdd((u64*)&cells[(size_t)k0 * kReachCells + i], (u64)v);
+  }
+  if ((int)threadIdx.x < kend - k0) {
+    const u64 v = accbest[threadIdx.x];
+    if (v != ~0ull) atomicMin((unsigned long long*)&best[k0 + threadIdx.x], (unsigned long long)v);
+  }
+  headroom_unsupported(s, k0, kend, [&](int k) { return task_spec[k]; }, cells + 10, kReachCells);
+}
+
+// the level of ONE ask on every node of the table (thread = node, as k_headroom_pod): -1 = never
+__global__ __launch_bounds__(kBlock) void k_preempt_reach_pod(NodeTable t, SpecTable s, ReclaimTable rc, int spec, int pin, int limit,
+                                                              unsigned pre_mask, unsigned filt_mask, int* __restrict__ out) {
+  int n = blockIdx.x * kBlock + threadIdx.x;
+  if (n >= t.n) return;
+  NodeRegs nr;
+  load_node(t, n, &nr);
+  i64 victims = 0;
+  const int level = reach_level(t, s, rc, spec, pin, n, nr, (i64)t.count[n], (i64)t.allowed[n], limit, pre_mask, filt_mask, &victims);
+  out[n] = level == kReachNever ? -1 : level;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Conflict-resolved decisions: the SEQUENTIAL loop yunikorn-core drives through the shim. For the asks of a
 // round, in order: the first node of the bin-pack order — under the state the EARLIER asks of the round left behind — that

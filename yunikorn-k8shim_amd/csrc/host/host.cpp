@@ -253,8 +253,15 @@ struct ykhost {
   DomainColumn domain_united;  // node-sharded handle: the cluster-wide value list and this shard's column over it, of the last call
   const std::vector<std::string>* domain_values_last = nullptr;  // the value list of the last ykhost_headroom_domains call
   int cfgR = 0, cfgKT = 0, cfgW = 0, cfgKD = -1, cfgKS = -1, cfgKP = -1;
+  // ---- preemption reach (ykhost_set_preemption_tiers): the tier bounds and the state of the device's reclaim table
+  std::vector<int32_t> rc_bounds;     // ascending; empty = the feature is off: nothing is derived, marked or uploaded
+  bool rc_uploaded = false;           // the engine holds the reclaim table of the current node table and bounds
+  std::vector<int> rc_dirty_nodes;    // nodes whose pod list changed since (one column each at the next reach call)
+  int64_t rc_uploads = 0, rc_patches = 0;
 
   void clear_state() {
+    rc_uploaded = false;
+    rc_dirty_nodes.clear();
     pool.clear();
     tpl_memo.clear();
     node_store.clear();
@@ -331,6 +338,7 @@ Pod* add_pod_object(ykhost* h, const mj::Value& v, size_t* anon) {
   }
   if (const mj::Value* spec = v.get_nn("spec")) p.node_name = spec->str_or("nodeName", "");
   if (p.uid.empty()) p.uid = "anon-" + std::to_string((*anon)++);
+  read_pod_preemption(v, &p);
   p.tpl = h->pool.intern(read_template(v));
   return store_pod(h, std::move(p));
 }
@@ -924,6 +932,8 @@ int full_sync(ykhost* h) {
   if (rc) return rc;
   rc = recreate_engine(h);
   if (rc) return rc;
+  h->rc_uploaded = false;  // (a new engine, or a node table of another size: the reclaim table goes with it)
+  h->rc_dirty_nodes.clear();
   rc = ykpred_set_row_stride(h->eng, h->row_stride_words);
   if (rc) return fail(h, std::string("ykpred_set_row_stride: ") + ykpred_last_error(h->eng), rc);
   rc = ykpred_set_row_capacity(h->eng, 0);  // (re-applied below: a smaller table may follow a larger one)
@@ -1058,6 +1068,7 @@ int sync(ykhost* h) {
 
 // A node-level change that cannot introduce new dictionary entries (pod assumed / forgotten / removed).
 void touch_node(ykhost* h, int n) {
+  if (h->rc_uploaded) h->rc_dirty_nodes.push_back(n);
   if (!h->dirty_all) {
     h->dirty_nodes.push_back(n);
     h->eval_dirty_nodes.push_back(n);
@@ -1695,6 +1706,9 @@ static int update_pod_text(ykhost* h, js::Range doc) {
   p.name = sc.name.str();
   p.terminating = sc.terminating;
   p.node_name = sc.node_name.str();
+  p.priority = sc.priority;
+  p.preempt_never = sc.preempt_never;
+  p.preempt_opt_out = sc.preempt_opt_out;
   if (p.uid.empty()) p.uid = "anon-" + std::to_string(h->pod_store.size());
   p.tpl = tpl;
   return apply_pod(h, store_pod(h, std::move(p)), sc.phase.str());
@@ -1719,7 +1733,7 @@ static int apply_pod(ykhost* h, Pod* p, const std::string& phase, Pod* hint) {
   // is: the reference's updatePod would take the pod off its node and put it back (scheduler_cache.go:321-360), with the same
   // sums, the same maps and nothing for a predicate to see; here it would also mark the node and the ask row for re-evaluation.
   if (old && old != p && !terminated && old->tpl == p->tpl && old->node_name == p->node_name && old->name == p->name &&
-      old->terminating == p->terminating && !old->assumed && !old->orphan && old->ask == wants_row &&
+      old->same_preemption(*p) && old->terminating == p->terminating && !old->assumed && !old->orphan && old->ask == wants_row &&
       (old->node_name.empty() || old->assigned_node == old->node_name)) {
     recycle_pod(h, p);
     return 1;
@@ -1833,6 +1847,9 @@ void scan_piece(const ykhost* h, SharedTemplates* shared, const char* b, const c
       sp.pod.name = sc.name.str();
       sp.pod.terminating = sc.terminating;
       sp.pod.node_name = sc.node_name.str();
+      sp.pod.priority = sc.priority;
+      sp.pod.preempt_never = sc.preempt_never;
+      sp.pod.preempt_opt_out = sc.preempt_opt_out;
       sp.phase = sc.phase.str();
       if (h->uid_index && !sp.pod.uid.empty()) sp.cached = h->by_uid.lookup(sp.pod.uid);
       if (sp.tpl_shard >= 0) out->shared_tpl.push_back((int32_t)out->pods.size() - 1);
@@ -3506,6 +3523,233 @@ int32_t ykhost_headroom_nodes(ykhost_t* h, int32_t pod, int32_t* out) {
 int32_t ykhost_headroom_by_key(ykhost_t* h, const char* allocation_key, int64_t* out16) {
   YKHOST_LOCKED(h);
   return headroom_by_key(h, "headroom", false, ykhost_headroom, allocation_key, out16, nullptr, 0);
+}
+
+// ---- preemption reach (ykpred_preempt_reach) ------------------------------------------------------------------------------------------
+namespace {
+// the tier of a pod that sits on a node, -1: in no tier (never a victim)
+int reclaim_tier(const ykhost* h, const Pod* p) {
+  if (p->preempt_opt_out) return -1;
+  for (size_t t = 0; t < h->rc_bounds.size(); ++t)
+    if (p->priority < h->rc_bounds[t]) return (int)t;
+  return -1;
+}
+// how many tiers lie wholly below the ask: every pod in them has strictly lower priority
+int32_t reclaim_limit(const ykhost* h, const Pod* p) {
+  if (p->preempt_never) return 0;
+  int32_t limit = 0;
+  for (int32_t b : h->rc_bounds) limit += b <= p->priority ? 1 : 0;
+  return limit;
+}
+// One node's column of the three planes, from NodeInfo.pods and used_ports: element (t, r) of `req` at req[(t * R + r) * stride], (t) of
+// `pods` at pods[t * stride], (t, k) of `ports` at ports[(t * KP + k) * stride] — stride N inside the table, 1 for a single column. The
+// ports follow NodeInfo.RemovePod as append_victims does: a tier's triples leave the SET, whoever else holds them.
+void reclaim_column(const ykhost* h, const NodeInfo& ni, size_t stride, int64_t* req, int32_t* pods, uint64_t* ports) {
+  const int T = (int)h->rc_bounds.size(), R = h->enc.R, KP = h->enc.KP;
+  for (int t = 0; t < T; ++t) {
+    for (int r = 0; r < R; ++r) req[((size_t)t * R + r) * stride] = 0;
+    pods[(size_t)t * stride] = 0;
+  }
+  std::vector<int> tier(ni.pods.size());
+  for (size_t i = 0; i < ni.pods.size(); ++i) {
+    const int t = tier[i] = reclaim_tier(h, ni.pods[i]);
+    if (t < 0) continue;
+    const Resource& r = ni.pods[i]->tpl->res;
+    int64_t* col = req + (size_t)t * R * stride;
+    col[0] += r.milli_cpu;
+    col[stride] += r.memory;
+    col[2 * stride] += r.ephemeral;
+    for (size_t s = 0; s < h->enc.scalar_names.size(); ++s) {
+      auto it = r.scalar.find(h->enc.scalar_names[s]);
+      if (it != r.scalar.end()) col[(3 + s) * stride] += it->second;
+    }
+    pods[(size_t)t * stride] += 1;
+  }
+  if (!KP || !ports) return;
+  std::set<HostPort> used = ni.used_ports;
+  std::vector<uint64_t> bits((size_t)KP);
+  bool changed = true;
+  for (int t = 0; t < T; ++t) {
+    for (size_t i = 0; i < ni.pods.size(); ++i)
+      if (tier[i] == t)
+        for (const HostPort& hp : template_host_ports(*ni.pods[i]->tpl)) changed = used.erase(hp) > 0 || changed;
+    if (changed) h->enc.encode_used_ports(used, bits.data());
+    changed = false;
+    for (int k = 0; k < KP; ++k) ports[((size_t)t * KP + k) * stride] = bits[(size_t)k];
+  }
+}
+void reclaim_planes(const ykhost* h, std::vector<int64_t>* req, std::vector<int32_t>* pods, std::vector<uint64_t>* ports) {
+  const size_t T = h->rc_bounds.size(), N = h->nodes.size();
+  req->assign(T * (size_t)h->enc.R * N + 1, 0);
+  pods->assign(T * N + 1, 0);
+  ports->assign(T * (size_t)h->enc.KP * N + 1, 0);
+  for (size_t n = 0; n < N; ++n) reclaim_column(h, *h->nodes[n], N, req->data() + n, pods->data() + n, ports->data() + n);
+}
+// sync, then the device's reclaim table: whole when it is not there (first use, new bounds, a re-created engine — a node was added or
+// removed), else one column per node whose pods changed
+int reclaim_sync(ykhost* h, const char* name) {
+  if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
+  if (h->rc_bounds.empty()) return fail(h, std::string(name) + ": no preemption tiers (ykhost_set_preemption_tiers)", YKPRED_E_STATE);
+  int rc = sync(h);
+  if (rc) return rc;
+  ykpred_reclaim_t rt{};
+  rt.tiers = (int32_t)h->rc_bounds.size();
+  if (!h->rc_uploaded) {
+    std::vector<int64_t> req;
+    std::vector<int32_t> pods;
+    std::vector<uint64_t> ports;
+    reclaim_planes(h, &req, &pods, &ports);
+    rt.requests = req.data();
+    rt.pods = pods.data();
+    rt.ports_after = h->enc.KP ? ports.data() : nullptr;
+    rc = ykpred_set_reclaim(h->eng, &rt);
+    if (rc) return fail(h, std::string("ykpred_set_reclaim: ") + ykpred_last_error(h->eng), rc);
+    h->rc_uploaded = true;
+    h->rc_uploads++;
+    h->rc_dirty_nodes.clear();
+    return 0;
+  }
+  std::vector<int> todo;
+  todo.swap(h->rc_dirty_nodes);
+  std::sort(todo.begin(), todo.end());
+  todo.erase(std::unique(todo.begin(), todo.end()), todo.end());
+  const size_t T = h->rc_bounds.size();
+  std::vector<int64_t> req(T * (size_t)h->enc.R + 1);
+  std::vector<int32_t> pods(T + 1);
+  std::vector<uint64_t> ports(T * (size_t)h->enc.KP + 1);
+  for (int n : todo) {
+    if (n < 0 || (size_t)n >= h->nodes.size()) continue;
+    reclaim_column(h, *h->nodes[(size_t)n], 1, req.data(), pods.data(), ports.data());
+    rt.requests = req.data();
+    rt.pods = pods.data();
+    rt.ports_after = h->enc.KP ? ports.data() : nullptr;
+    rc = ykpred_update_reclaim_node(h->eng, n, &rt);
+    if (rc) {
+      h->rc_uploaded = false;  // (the next call uploads the whole table)
+      return fail(h, std::string("ykpred_update_reclaim_node: ") + ykpred_last_error(h->eng), rc);
+    }
+    h->rc_patches++;
+  }
+  return 0;
+}
+}  // namespace
+
+int32_t ykhost_set_preemption_tiers(ykhost_t* h, const int32_t* bounds, int32_t T) {
+  YKHOST_LOCKED(h);
+  if (T < 0 || T > YKPRED_REACH_MAX_TIERS || (T > 0 && !bounds)) return fail(h, "set_preemption_tiers: 0 .. 8 tiers", YKPRED_E_INVALID);
+  for (int t = 1; t < T; ++t)
+    if (bounds[t] <= bounds[t - 1]) return fail(h, "set_preemption_tiers: the bounds must ascend strictly", YKPRED_E_INVALID);
+  h->rc_bounds.assign(bounds, bounds + T);
+  h->rc_uploaded = false;
+  h->rc_dirty_nodes.clear();
+  if (T == 0 && h->eng) ykpred_set_reclaim(h->eng, nullptr);
+  return 0;
+}
+
+int32_t ykhost_reclaim_table(ykhost_t* h, int32_t* dims, int64_t* requests, int32_t* pods, uint64_t* ports_after) {
+  YKHOST_LOCKED(h);
+  if (!dims) return fail(h, "reclaim_table: bad argument", -1);
+  if (h->rc_bounds.empty()) return fail(h, "reclaim_table: no preemption tiers (ykhost_set_preemption_tiers)", YKPRED_E_STATE);
+  int rc = 0;
+  if (h->device < 0) {  // (a mirror-only handle encodes for the dictionaries alone, as ykhost_encoded_tables_json does)
+    EncodedTables T;
+    rc = encode_tables(h, &T);
+    h->dirty_all = true;
+  } else {
+    rc = sync(h);
+  }
+  if (rc) return rc;
+  const size_t T = h->rc_bounds.size(), N = h->nodes.size(), R = (size_t)h->enc.R, KP = (size_t)h->enc.KP;
+  dims[0] = (int32_t)T, dims[1] = (int32_t)R, dims[2] = (int32_t)KP, dims[3] = (int32_t)N;
+  if (!requests || !pods || !ports_after) return 0;
+  std::vector<int64_t> q;
+  std::vector<int32_t> c;
+  std::vector<uint64_t> pa;
+  reclaim_planes(h, &q, &c, &pa);
+  std::copy(q.begin(), q.begin() + (long)(T * R * N), requests);
+  std::copy(c.begin(), c.begin() + (long)(T * N), pods);
+  std::copy(pa.begin(), pa.begin() + (long)(T * KP * N), ports_after);
+  return 0;
+}
+
+int32_t ykhost_preempt_reach(ykhost_t* h, int32_t n, const int32_t* asks, int64_t* out_cells) {
+  YKHOST_LOCKED(h);
+  constexpr size_t B = YKPRED_REACH_CELLS;
+  if (n < 0 || (n > 0 && !out_cells)) return fail(h, "preempt_reach: bad argument", -1);
+  int rc = reclaim_sync(h, "preempt_reach");
+  if (rc) return rc;
+  int32_t world = 1;
+  ykpred_comm_info(h->eng, nullptr, &world, nullptr);
+  const int P = (int)h->pending.size();
+  for (int i = 0; i < n; ++i)
+    if ((asks ? asks[i] : i) < 0 || (asks ? asks[i] : i) >= P) return fail(h, "preempt_reach: ask index out of range", YKPRED_E_INVALID);
+  // (an ask routed to the CPU manager gets its status here; on a node-sharded handle every ask goes to the engine, as in ykhost_explain)
+  std::vector<int32_t> list, limits, slot;
+  for (int i = 0; i < n; ++i) {
+    const int row = asks ? asks[i] : i;
+    const Pod* p = h->pending[(size_t)row];
+    int64_t* c = out_cells + (size_t)i * B;
+    if (world <= 1 && h->enc.unsupported.count(p->tpl)) {
+      std::fill(c, c + B, (int64_t)0);
+      c[10] = 1;
+      c[11] = reclaim_limit(h, p);
+      c[13] = -1;
+    } else {
+      list.push_back(row);
+      limits.push_back(reclaim_limit(h, p));
+      slot.push_back(i);
+    }
+  }
+  if (list.empty() && world <= 1) return 0;
+  std::vector<int64_t> rows(list.size() * B);
+  rc = ykpred_preempt_reach(h->eng, (int32_t)list.size(), list.data(), limits.data(), h->alloc_pre, h->alloc_filt, rows.data());
+  if (rc) return fail(h, std::string("ykpred_preempt_reach: ") + ykpred_last_error(h->eng), rc);
+  for (size_t k = 0; k < list.size(); ++k) memcpy(out_cells + (size_t)slot[k] * B, rows.data() + k * B, B * sizeof(int64_t));
+  return 0;
+}
+
+int32_t ykhost_preempt_limits(ykhost_t* h, int32_t n, const int32_t* asks, int32_t* out_limits) {
+  YKHOST_LOCKED(h);
+  if (n < 0 || (n > 0 && !out_limits)) return fail(h, "preempt_limits: bad argument", -1);
+  int rc = reclaim_sync(h, "preempt_limits");
+  if (rc) return rc;
+  for (int i = 0; i < n; ++i) {
+    const int row = asks ? asks[i] : i;
+    if (row < 0 || row >= (int)h->pending.size()) return fail(h, "preempt_limits: ask index out of range", YKPRED_E_INVALID);
+    out_limits[i] = reclaim_limit(h, h->pending[(size_t)row]);
+  }
+  return 0;
+}
+
+int32_t ykhost_preempt_reach_nodes(ykhost_t* h, int32_t pod, int32_t* out) {
+  YKHOST_LOCKED(h);
+  if (!out) return fail(h, "preempt_reach_nodes: bad argument", -1);
+  int rc = reclaim_sync(h, "preempt_reach_nodes");
+  if (rc) return rc;
+  if (pod < 0 || pod >= (int)h->pending.size()) return fail(h, "preempt_reach_nodes: ask index out of range", YKPRED_E_INVALID);
+  rc = ykpred_preempt_reach_pod(h->eng, pod, reclaim_limit(h, h->pending[(size_t)pod]), h->alloc_pre, h->alloc_filt, out);
+  if (rc) return fail(h, std::string("ykpred_preempt_reach_pod: ") + ykpred_last_error(h->eng), rc);
+  return 0;
+}
+
+// One ask named as the core names it, one crossing: the cells, and the best node by name — in front of the node walk that ends in
+// IsPodFitNodeViaPreemption.
+int32_t ykhost_preempt_reach_by_key(ykhost_t* h, const char* allocation_key, int64_t* out16, char* best_node_name, int64_t len) {
+  YKHOST_LOCKED(h);
+  if (!out16) return fail(h, "preempt_reach_by_key: bad argument", -1);
+  std::fill(out16, out16 + YKPRED_REACH_CELLS, (int64_t)0);
+  out16[13] = -1;
+  copy_out("", best_node_name, len);
+  int32_t row = -1;
+  int rc = ask_row_by_key(h, allocation_key, &out16[10], &row);
+  if (rc) return rc;
+  rc = ykhost_preempt_reach(h, 1, &row, out16);
+  if (rc || !best_node_name) return rc;
+  int32_t offset = 0;
+  ykpred_comm_info(h->eng, nullptr, nullptr, &offset);
+  const int64_t local = out16[13] - offset;
+  if (out16[13] >= 0 && local >= 0 && local < (int64_t)h->nodes.size()) copy_out(h->nodes[(size_t)local]->node.name, best_node_name, len);
+  return 0;
 }
 
 // ---- headroom per topology domain (ykpred_headroom_groups) --------------------------------------------------------------------------

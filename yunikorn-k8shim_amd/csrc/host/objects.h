@@ -130,8 +130,14 @@ struct Pod {
   bool ask = false;           // holds a row of the ask table (bitmap row); rows stay put across AssumePod / ForgetPod
   int32_t row = -1;           // that row
   int32_t remote_node = -1;   // assumed by a round of a node-sharded cluster on ANOTHER shard's node: its index in the whole cluster
+  // What preemption reads of a pod (kept per pod, not per template: pods of one template may carry different priorities)
+  int32_t priority = 0;         // spec.priority, 0 when missing (si_helper.go:68-72)
+  bool preempt_never = false;   // spec.preemptionPolicy == "Never": the pod preempts nobody (task.go:256-269)
+  bool preempt_opt_out = false; // annotation yunikorn.apache.org/allow-preemption: "false": never a victim (task.go:244-254)
   const PodTemplate* tpl = nullptr;
+  bool same_preemption(const Pod& o) const { return priority == o.priority && preempt_never == o.preempt_never && preempt_opt_out == o.preempt_opt_out; }
 };
+constexpr const char* kAllowPreemptionAnnotation = "yunikorn.apache.org/allow-preemption";
 
 struct Node {
   std::string name;
@@ -560,6 +566,7 @@ inline void pod_json(const Pod& p, std::string& o, int replicas = 1) {
   js_str(o, p.uid);
   o += ",";
   o += meta;
+  if (p.preempt_opt_out) o += std::string(",\"annotations\":{\"") + kAllowPreemptionAnnotation + "\":\"false\"}";
   if (p.terminating) o += ",\"deletionTimestamp\":\"2026-01-01T00:00:00Z\"";
   o += "},\"spec\":{";
   if (!p.node_name.empty()) {
@@ -567,6 +574,8 @@ inline void pod_json(const Pod& p, std::string& o, int replicas = 1) {
     js_str(o, p.node_name);
     o += ",";
   }
+  if (p.priority != 0) o += "\"priority\":" + std::to_string(p.priority) + ",";
+  if (p.preempt_never) o += "\"preemptionPolicy\":\"Never\",";
   o += spec;
   o += "}";
   if (replicas > 1) o += ",\"replicas\":" + std::to_string(replicas);
@@ -601,7 +610,9 @@ inline void node_json(const NodeInfo& ni, std::string& o, bool compact = false) 
     if (i) o.push_back(',');
     size_t run = 1;
     if (compact && !ni.pods[i]->terminating)
-      while (i + run < ni.pods.size() && ni.pods[i + run]->tpl == ni.pods[i]->tpl && !ni.pods[i + run]->terminating) ++run;
+      while (i + run < ni.pods.size() && ni.pods[i + run]->tpl == ni.pods[i]->tpl && !ni.pods[i + run]->terminating &&
+             ni.pods[i + run]->same_preemption(*ni.pods[i]))
+        ++run;
     pod_json(*ni.pods[i], o, (int)run);
     i += run;
   }
@@ -844,6 +855,18 @@ inline PodTemplate read_template(const mj::Value& v) {
       t.spread.push_back(std::move(sc));
     }
   return t;
+}
+
+// spec.priority, spec.preemptionPolicy and the allow-preemption annotation of a pod document
+inline void read_pod_preemption(const mj::Value& v, Pod* p) {
+  p->priority = 0;
+  p->preempt_never = p->preempt_opt_out = false;
+  if (const mj::Value* spec = v.get_nn("spec")) {
+    p->priority = (int32_t)spec->int_or("priority", 0);
+    p->preempt_never = spec->str_or("preemptionPolicy", "") == "Never";
+  }
+  if (const mj::Value* md = v.get_nn("metadata"))
+    if (const mj::Value* an = md->get_nn("annotations")) p->preempt_opt_out = an->is_obj() && an->str_or(kAllowPreemptionAnnotation, "") == "false";
 }
 
 inline Node read_node(const mj::Value& v) {

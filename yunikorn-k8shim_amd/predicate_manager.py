@@ -54,6 +54,10 @@ SPREAD_HEADROOM_CELLS, SPREAD_ROW_CELLS = 16, 4
 # domains, copies outside, nodes outside, domains filled / cut, 0, the domain with the most copies, topology key index, mode (0 static,
 # 1 one per domain, 2 bootstrap), fitting nodes, 0; per (ask, domain) int64[SPREAD_ROW_CELLS] = cnt, cap, nodes, copies
 AFFINITY_HEADROOM_CELLS = 16
+# ykpred_preempt_reach: per ask int64[REACH_CELLS] = nodes at level 0, 1..8, never, status (0 computed, 1 routed), the ask's limit, the
+# lowest level >= 1 with a node (0: none), the best node at it (fewest victim pods, lowest index; -1: none), its victim pods, 0
+REACH_CELLS, REACH_MAX_TIERS = 16, 8
+REACH_NEVER, REACH_STATUS, REACH_LIMIT, REACH_BEST_LEVEL, REACH_BEST_NODE, REACH_BEST_PODS = 9, 10, 11, 12, 13, 14
 
 
 def plugin_mask(names):
@@ -725,6 +729,73 @@ class GpuPredicateManager:
             pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
             self._pcheck(self._P.ykpred_headroom_pod(self.engine, int(p), pre, filt, out.ctypes.data))
         return out[:self.num_nodes].copy()
+
+    # ---- preemption reach: which nodes removing lower-priority pods opens ----------------------------------------------
+    def set_preemption_tiers(self, bounds):
+        """Ascending priority bounds b[0] < ... < b[T-1], T <= REACH_MAX_TIERS (ykhost_set_preemption_tiers): a pod on a node is in
+        tier t = the smallest t with priority < b[t]; an empty list switches the feature off and drops the device table."""
+        b = np.ascontiguousarray(list(bounds), dtype=np.int32)
+        self._check(self._L.ykhost_set_preemption_tiers(self._h, b.ctypes.data if len(b) else None, len(b)))
+
+    def preempt_reach(self, pods=None, pre_mask=None, filt_mask=None):
+        """Per ask the nodes by preemption LEVEL, reduced on the device (ykpred_preempt_reach): np.int64[n, REACH_CELLS] —
+        [0] nodes the ask fits as they stand, [L] nodes it fits once every pod of tiers < L is gone (1 <= L <= its limit),
+        [REACH_NEVER] nodes no removal opens, [REACH_STATUS] 1 for a routed ask, [REACH_LIMIT] the ask's limit,
+        [REACH_BEST_LEVEL], [REACH_BEST_NODE] (global index, -1: none), [REACH_BEST_PODS]. pods: ask indices or UIDs in any order,
+        repeats allowed; None = every ask. Always the allocation-phase lists; explicit masks go to the engine with the limits the
+        host derives. Needs no evaluation and disturbs none."""
+        if pods is None:
+            count, ptr = self.num_pods, None
+        else:
+            idx = [p if isinstance(p, (int, np.integer)) else self.pod_index(p) for p in pods]
+            arr = np.ascontiguousarray(idx, dtype=np.int32)
+            count, ptr = len(arr), arr.ctypes.data
+        out = np.zeros((max(count, 1), REACH_CELLS), dtype=np.int64)
+        if pre_mask is None and filt_mask is None:
+            self._check(self._L.ykhost_preempt_reach(self._h, count, ptr, out.ctypes.data))
+        else:
+            pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
+            limits = np.zeros(max(count, 1), dtype=np.int32)
+            self._check(self._L.ykhost_preempt_limits(self._h, count, ptr, limits.ctypes.data))  # (syncs the tables and the reclaim table)
+            if ptr is None:
+                arr = np.arange(count, dtype=np.int32)
+                ptr = arr.ctypes.data
+            self._pcheck(self._P.ykpred_preempt_reach(self.engine, count, ptr, limits.ctypes.data, pre, filt, out.ctypes.data))
+        return out[:count].copy()
+
+    def preempt_reach_nodes(self, pod):
+        """The level of ONE ask (index or UID) on every node (ykpred_preempt_reach_pod): np.int32[N], -1 = never — the shortlist
+        to walk for the real victim selection. On a node-sharded manager: this shard's nodes."""
+        p = pod if isinstance(pod, (int, np.integer)) else self.pod_index(pod)
+        out = np.zeros(max(self.num_nodes, 1), dtype=np.int32)
+        self._check(self._L.ykhost_preempt_reach_nodes(self._h, int(p), out.ctypes.data))
+        return out[:self.num_nodes].copy()
+
+    def preempt_reach_by_key(self, uid):
+        """One ask by allocation key in one crossing (ykhost_preempt_reach_by_key) → (np.int64[REACH_CELLS], best node name or "").
+        Raises UnsupportedAsk for a routed ask, KeyError for an unknown pod."""
+        out = np.zeros(REACH_CELLS, dtype=np.int64)
+        buf = C.create_string_buffer(512)
+        rc = self._L.ykhost_preempt_reach_by_key(self._h, uid.encode(), out.ctypes.data, buf, 512)
+        if rc == -13:
+            raise UnsupportedAsk(self._L.ykhost_last_error(self._h).decode())
+        if rc in (-10, -12):
+            raise KeyError(uid)
+        self._check(rc)
+        return out, buf.value.decode()
+
+    def reclaim_table(self):
+        """The reclaim planes the mirror derives from the pods on its nodes (ykhost_reclaim_table; works without a device) →
+        (requests np.int64[T, R, N], pods np.int32[T, N], ports_after np.uint64[T, KP, N])."""
+        dims = np.zeros(4, dtype=np.int32)
+        self._check(self._L.ykhost_reclaim_table(self._h, dims.ctypes.data, None, None, None))
+        T, R, KP, N = (int(x) for x in dims)
+        req = np.zeros((T, R, N), dtype=np.int64)
+        cnt = np.zeros((T, N), dtype=np.int32)
+        ports = np.zeros((T, KP, N), dtype=np.uint64)
+        pad = [np.zeros(1, dtype=a.dtype) if a.size == 0 else a for a in (req, cnt, ports)]
+        self._check(self._L.ykhost_reclaim_table(self._h, dims.ctypes.data, *(a.ctypes.data for a in pad)))
+        return req, cnt, ports
 
     def headroom_domains(self, pods=None, label_key=None, node_group=None, num_groups=None, want=None, groups=False, pre_mask=None,
                          filt_mask=None):
