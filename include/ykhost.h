@@ -352,6 +352,24 @@ int32_t ykhost_reclaim_table(ykhost_t* h, int32_t* dims /* [4] */, int64_t* requ
  * ykhost_preempt_reach and without an engine query: what a caller of ykpred_preempt_reach with plugin lists of its own passes on. */
 int32_t ykhost_preempt_limits(ykhost_t* h, int32_t n, const int32_t* asks /* NULL = asks 0..n-1 */, int32_t* out_limits /* [n] */);
 
+/* PREEMPTION HEADROOM (ykpred.h: ykpred_preempt_headroom) — can preemption up to the ask's priority place the whole gang, at which level,
+ * and at the cost of how many resident pods? — asked where a task group creates its minMember placeholders, before the timeout wait.
+ * The tiers are those of ykhost_set_preemption_tiers, the limits are derived and the reclaim table is kept up to date exactly as for
+ * ykhost_preempt_reach; always the ALLOCATION-phase plugin lists.
+ *   ykhost_preempt_headroom         ONE engine call for the listed asks (NULL = asks 0..n-1) with their wants (NULL = 1 each; a want
+ *                                   < 1 is YKPRED_E_INVALID): out_cells[i] = the YKPRED_PREEMPT_HEADROOM_CELLS cells. An ask routed to the
+ *                                   CPU manager gets status [27] = 1 without a device call. YKPRED_E_STATE without tiers. Collective on a
+ *                                   node-sharded handle: every rank passes the same asks and wants.
+ *   ykhost_preempt_headroom_nodes   rep_L of ONE ask on every node, L = 0..limit (ykpred_preempt_headroom_pod): out holds
+ *                                   [limit+1][N] — size it for [tiers+1][N] —, *out_limit the ask's limit; this shard's nodes on a
+ *                                   node-sharded handle.
+ *   ykhost_preempt_headroom_by_key  ONE crossing for one ask by allocation key (pod UID) and its want: the 32 cells. → 0, or the
+ *                                   errors of ykhost_headroom_by_key (YKHOST_E_UNSUPPORTED with out32[27] = 1). */
+int32_t ykhost_preempt_headroom(ykhost_t* h, int32_t n, const int32_t* asks /* NULL = asks 0..n-1 */, const int64_t* wants /* NULL = 1 */,
+                                int64_t* out_cells /* [n][32] */);
+int32_t ykhost_preempt_headroom_nodes(ykhost_t* h, int32_t pod, int32_t* out /* [limit+1][N] */, int32_t* out_limit);
+int32_t ykhost_preempt_headroom_by_key(ykhost_t* h, const char* allocation_key, int64_t want, int64_t* out32 /* [32] */);
+
 /* Engine calls that came back YKPRED_E_DEVICE / YKPRED_E_NOMEM so far (failed allocation, lost device). Each one marks the whole
  * device state stale: the failing call returns its error (Predicates() < 0: the Go manager routes the ask to the CPU predicate
  * manager — SURVEY.md §5, "must degrade, never fail scheduling"), the mirror stays intact, and the next ykhost_sync /

@@ -38,7 +38,9 @@
 extern "C" {
 #endif
 
-/* (ykpred_preempt_reach + ykpred_preempt_reach_pod + ykpred_set_reclaim + ykpred_update_reclaim_node + YKPRED_REACH_CELLS arrived
+/* (ykpred_preempt_headroom + ykpred_preempt_headroom_pod + YKPRED_PREEMPT_HEADROOM_CELLS arrived WITHIN version 4 too:
+ *    dlsym("ykpred_preempt_headroom"))
+ * (ykpred_preempt_reach + ykpred_preempt_reach_pod + ykpred_set_reclaim + ykpred_update_reclaim_node + YKPRED_REACH_CELLS arrived
  *    WITHIN version 4 too: dlsym("ykpred_preempt_reach"))
  * (ykpred_headroom_affinity + ykpred_headroom_affinity_pod + YKPRED_AFFINITY_HEADROOM_CELLS arrived WITHIN version 4 too:
  *    dlsym("ykpred_headroom_affinity"))
@@ -730,6 +732,46 @@ int32_t ykpred_preempt_reach(ykpred_engine_t* e, int32_t n_asks, const int32_t* 
  * the real victim selection. -1 everywhere for a YKPRED_SPEC_UNSUPPORTED spec. This shard's nodes only on a sharded engine. */
 int32_t ykpred_preempt_reach_pod(ykpred_engine_t* e, int32_t pod_index, int32_t limit, uint32_t prefilter_plugins, uint32_t filter_plugins,
                                  int32_t* out /* [N] */);
+
+/* PREEMPTION HEADROOM — how many copies of an ask the cluster takes per preemption level: can preemption up to the ask's priority place
+ * the whole gang, what is the lowest level at which it can, and how many resident pods would that cost?
+ *
+ * For a node n and a level L in 0..limit, state_L(n) is the node with ALL pods of tiers < L gone, exactly as ykpred_preempt_reach removes
+ * them: free resources grow by the summed request vectors of those tiers, len(Pods) drops by their pod counts, the port words become
+ * ports_after[L-1] (where the plane exists and L >= 1), the PreFilter state of the topology plugins stays frozen.
+ * rep_L(a, n) = ykpred_headroom's replicas(a, n) evaluated on state_L(n) by the same device routine: 0 when Predicates() rejects the
+ * pair there, else min(free pod slots, min over r with req_r > 0 of floor(free_r / req_r)) in exact int64 arithmetic, cut to 1 when the
+ * spec requests a dictionary host port and NodePorts is in both lists. Hence rep_0 == ykpred_headroom_pod, rep_L is non-decreasing in
+ * L, and min{L : rep_L >= 1} == ykpred_preempt_reach_pod (-1 <=> rep_limit == 0). */
+#define YKPRED_PREEMPT_HEADROOM_CELLS 32
+/* per ask, int64[32], over all nodes of the table, with m(L) = min(L, limit):
+ *  [0..8]   copies(L)  = sum over n of rep_m(L)(a, n), L = 0..8 (flat above the limit)
+ *  [9..17]  nodes(L)   = nodes with rep_m(L) >= 1 (the prefix sums of ykpred_preempt_reach cells [0..8])
+ *  [18..26] victims(L) = sum over n of gone(n, l*(n, L)): gone(n, l) = the pods of n in tiers < l, l*(n, L) = the smallest l <= m(L)
+ *           with rep_l == rep_m(L) — the pods of the FEWEST whole tiers that give each node its level-L copies; a tier that frees
+ *           something but adds no copy is not charged by itself. victims(0) == 0.
+ *  [27]     status: 0 computed; 1 the ask's spec is YKPRED_SPEC_UNSUPPORTED (every cell but [27..29] is 0); 2 coupled, by exactly
+ *           ykpred_headroom's rule: copies(.) and victims(.) are -1, nodes(.) are still the single-copy fit counts, [30] == -1
+ *  [28]     the limit, echoed
+ *  [29]     the want, echoed
+ *  [30]     the lowest L <= limit with copies(L) >= want, or -1
+ *  [31]     0
+ * Invariants at status 0: copies(0) == ykpred_headroom [0]; nodes(L) <= copies(L); all three rows are non-decreasing.
+ * wants == NULL means 1 for every ask. The tasks are the distinct (spec, NodeName, limit) of the list: the want multiplies no task, it
+ *   is read only when the per-level table is finished on the host.
+ * Everything else is ykpred_preempt_reach's: the call reads the TABLES only, needs no evaluation and invalidates none; it prepares the
+ *   topology histograms as ykpred_query does; it counts as one query; roctx range "ykpred:preempt_headroom"; YKPRED_E_STATE without a
+ *   reclaim table; YKPRED_E_INVALID for a limit outside 0..T, a want < 1, or NodeResourcesFit missing from either list (as
+ *   ykpred_headroom). n_asks == 0 is OK; N == 0 gives zero rows with [30] == -1.
+ * NODE-SHARDED engines: COLLECTIVE — the agreement all-gather first (it covers the limits and the wants), then exactly ONE all-reduce SUM
+ *   (int64) of the per-level table; the prefix sums and [30] are derived after it, on every rank alike: CLUSTER-WIDE cells. */
+int32_t ykpred_preempt_headroom(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks /* host, ask indices, any order, repeats allowed */,
+                                const int32_t* limits /* host, [n_asks], 0..T */, const int64_t* wants /* host, [n_asks], >= 1; NULL = 1 */,
+                                uint32_t prefilter_plugins, uint32_t filter_plugins, int64_t* out /* host, [n_asks][YKPRED_PREEMPT_HEADROOM_CELLS] */);
+/* Row L of out = rep_L(pod, n) for every node n of the table, L = 0..limit. -1 everywhere for a coupled ask, 0 for a
+ * YKPRED_SPEC_UNSUPPORTED spec. This shard's nodes only on a sharded engine. */
+int32_t ykpred_preempt_headroom_pod(ykpred_engine_t* e, int32_t pod_index, int32_t limit, uint32_t prefilter_plugins, uint32_t filter_plugins,
+                                    int32_t* out /* [limit+1][N] */);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Multi-GPU: node-axis shards. One engine per GPU / process holds a contiguous shard of the node table and

@@ -643,6 +643,40 @@ func (m *gpuPredicateManager) PreemptionReach(pod *v1.Pod) (fits, reachable, nev
 	}
 }
 
+// PreemptionHeadroom answers, for a gang of `want` identical placeholders, whether preemption up to the ask's priority can place all of
+// them, the lowest level at which it can, and what that costs: cells[0..8] the copies the cluster takes once every pod of the tiers
+// below level L is gone, cells[9..17] the nodes that take at least one, cells[18..26] the resident pods of the fewest whole tiers that
+// give those copies, cells[27] the status (2: the ask's copies interact through a topology constraint, no count), cells[28] the ask's
+// limit, cells[30] the lowest level whose copies meet want, or -1. The call site is beside PreemptionReach, one step earlier: where a
+// task group creates its minMember placeholders, before the wait for the placeholder timeout — with cells[30] == -1 the gang cannot
+// be placed by any preemption the ask is entitled to, and the application can be failed or resized at once. ONE crossing:
+// ykhost_preempt_headroom_by_key looks the ask up by allocation key. ok == false when the pod is not a mirrored ask, is routed to the
+// CPU predicate manager, no tiers are set, want < 1 or the engine failed: the caller waits as before.
+func (m *gpuPredicateManager) PreemptionHeadroom(allocationKey string, want int64) (cells [32]int64, ok bool) {
+	var out [32]C.int64_t
+	key := C.CString(allocationKey)
+	rc := C.ykhost_preempt_headroom_by_key(m.host, key, C.int64_t(want), &out[0])
+	C.free(unsafe.Pointer(key))
+	for i := range out {
+		cells[i] = int64(out[i])
+	}
+	switch {
+	case rc == 0:
+		return cells, cells[27] != 1
+	case rc == C.YKHOST_E_UNSUPPORTED:
+		m.Counters.RoutedUnsupported.Add(1)
+		return cells, false
+	case rc == C.YKHOST_E_POD_NOT_FOUND || rc == C.YKHOST_E_NOT_AN_ASK:
+		m.Counters.RoutedNotMirrored.Add(1)
+		return cells, false
+	default:
+		m.Counters.RoutedOnError.Add(1)
+		log.Log(log.ShimPredicates).Warn("GPU predicate engine error, no preemption headroom for the ask",
+			zap.String("error", C.GoString(C.ykhost_last_error(m.host))))
+		return cells, false
+	}
+}
+
 // ResidentStats: Predicates() calls answered from the mirrored resident answer, per pair because the node's column changed,
 // by whole-ask device queries, and the answer / failing-plugin fetches behind them.
 func (m *gpuPredicateManager) ResidentStats() (resident, dirtyColumn, query, answerFetches, codeFetches int64) {

@@ -10,6 +10,8 @@ from .predicate_manager import (ALL_PLUGINS, EXPLAIN_BINS, EXPLAIN_FIT, EXPLAIN_
                                 HEADROOM_MAX, HEADROOM_NODES, HEADROOM_STATUS, HEADROOM_TOTAL, PLUGIN_BITS, SPREAD_HEADROOM_CELLS, SPREAD_ROW_CELLS,
                                 AFFINITY_HEADROOM_CELLS,
                                 REACH_BEST_LEVEL, REACH_BEST_NODE, REACH_BEST_PODS, REACH_CELLS, REACH_LIMIT, REACH_MAX_TIERS, REACH_NEVER, REACH_STATUS,
+                                PREEMPT_HEADROOM_CELLS, PREEMPT_HEADROOM_COPIES, PREEMPT_HEADROOM_LEVEL, PREEMPT_HEADROOM_LIMIT, PREEMPT_HEADROOM_NODES,
+                                PREEMPT_HEADROOM_STATUS, PREEMPT_HEADROOM_VICTIMS, PREEMPT_HEADROOM_WANT,
                                 GpuPredicateManager,
                                 PredicateError, UnsupportedAsk, plugin_mask)
 

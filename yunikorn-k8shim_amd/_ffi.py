@@ -153,6 +153,8 @@ def load_ykpred():
     L.ykpred_update_reclaim_node.argtypes = [C.c_void_p, C.c_int32, C.POINTER(YkpredReclaim)]
     L.ykpred_preempt_reach.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     L.ykpred_preempt_reach_pod.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.ykpred_preempt_headroom.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.ykpred_preempt_headroom_pod.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
     _pred = L
     return L
 
@@ -246,6 +248,9 @@ def load_ykhost():
     L.ykhost_preempt_reach_by_key.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_char_p, C.c_int64]
     L.ykhost_preempt_limits.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.ykhost_reclaim_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ykhost_preempt_headroom.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ykhost_preempt_headroom_nodes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.ykhost_preempt_headroom_by_key.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p]
     L.ykhost_device_errors.restype = C.c_int64
     L.ykhost_device_errors.argtypes = [C.c_void_p]
     _host = L

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "kernels.hip.h"
+#include "preempt_headroom_finish.h"
 
 using ykk::i64;
 using ykk::u64;
@@ -279,6 +280,7 @@ struct ykpred_engine {
   DevBuf d_groups;  // ykpred_headroom_groups: summaries | pair wants | pair tasks | task specs | task pins | coupled | node groups | one table chunk
   DevBuf d_domain_head;  // headroom_domains_run (ykpred_headroom_spread, _affinity): summaries | tasks | one table chunk (rows | extra cells)
   DevBuf d_reach;  // ykpred_preempt_reach: [tasks][YKPRED_REACH_CELLS] cells | [tasks] best keys | task specs | task pins | task limits
+                   // ykpred_preempt_headroom: [tasks][YKPRED_PREEMPT_HEADROOM_CELLS] per-level deltas | task specs | task pins | task limits
   // the resident reclaim table (ykpred_set_reclaim): what the pods of each priority tier give back per node
   DevBuf d_rc_req, d_rc_pods, d_rc_ports;  // [T][R][N] i64; [T][N] int; [T][KP][N] u64 (only with rc_ports)
   int rc_tiers = 0;                        // 0 = no table
@@ -4917,6 +4919,99 @@ int32_t ykpred_preempt_reach_pod(ykpred_engine_t* e, int32_t pod, int32_t limit,
                      spec_table(e), reclaim_table(e), e->h_pod_spec[(size_t)pod], e->h_pod_pin[(size_t)pod], limit, pre, filt, e->d_scratch.as<int32_t>());
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, e->d_scratch.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return YKPRED_OK;
+}
+
+// Copies of an ask per preemption level: ykpred_headroom's replicas on the node states of ykpred_preempt_reach, reduced per level on the
+// device (k_preempt_headroom). The driver of ykpred_preempt_reach — tasks keyed with the limit, the agreement, ONE SUM reduce of the
+// per-level deltas — and then the finish of preempt_headroom_finish.h per listed ask, on every rank alike: the want is read only there.
+int32_t ykpred_preempt_headroom(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, const int32_t* limits, const int64_t* wants, uint32_t pre,
+                                uint32_t filt, int64_t* out) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:preempt_headroom");
+  if (e) e->n_queries++;
+  static_assert(ykk::kPreemptHeadroomCells == YKPRED_PREEMPT_HEADROOM_CELLS && ykfinish::kPreemptHeadroomCells == YKPRED_PREEMPT_HEADROOM_CELLS &&
+                    ykfinish::kPreemptHeadroomLevels == YKPRED_REACH_MAX_TIERS + 1,
+                "k_preempt_headroom and the finish write the layout of ykpred.h");
+  constexpr size_t B = YKPRED_PREEMPT_HEADROOM_CELLS;
+  if (!e) return YKPRED_E_INVALID;
+  const bool args_ok = n_asks <= 0 || (asks && limits && out);
+  auto more_checks = [&](std::string* why) -> int {
+    if (e->rc_tiers == 0) return *why = "preempt_headroom: no reclaim table (ykpred_set_reclaim)", YKPRED_E_STATE;
+    for (int i = 0; i < n_asks; ++i)
+      if (limits[i] < 0 || limits[i] > e->rc_tiers) return *why = "preempt_headroom: limit outside 0 .. tiers", YKPRED_E_INVALID;
+    if (wants)
+      for (int i = 0; i < n_asks; ++i)
+        if (wants[i] < 1) return *why = "preempt_headroom: want below 1", YKPRED_E_INVALID;
+    return YKPRED_OK;
+  };
+  u64 more = tune_hash({(u64)(uint32_t)e->rc_tiers});
+  if (n_asks > 0 && args_ok)
+    for (int i = 0; i < n_asks; ++i) more = tune_hash({(u64)(uint32_t)limits[i], (u64)(wants ? wants[i] : 1)}, more);
+  HeadroomTasks tasks;
+  tasks.extra = args_ok && n_asks > 0 ? limits : nullptr;
+  tasks.other_causes = "bad argument, NodeResourcesFit missing from a list, no reclaim table, a limit outside 0 .. tiers, a want below 1, tables not uploaded, an index out of range or stale topology histograms";
+  bool run = false;
+  const int32_t rc = headroom_prepare(e, "preempt_headroom", n_asks, asks, args_ok, pre, filt, more_checks, more, &tasks, &run);
+  if (!run) return rc;
+  const bool sharded = e->comm && e->comm_world > 1;
+  const std::vector<int32_t>&task_of = tasks.task_of, &t_spec = tasks.spec, &t_pin = tasks.pin, &t_limit = tasks.extra_of;
+  hipStream_t st = e->own_stream;
+  const size_t T = t_spec.size();
+  HIPCHK(e->d_reach.ensure(T * (B * sizeof(int64_t) + 3 * sizeof(int32_t)) + 64));
+  int64_t* d_cells = e->d_reach.as<int64_t>();
+  int32_t* d_spec = (int32_t*)(d_cells + T * B);
+  int32_t* d_pin = d_spec + T;
+  int32_t* d_limit = d_pin + T;
+  HIPCHK(hipMemsetAsync(d_cells, 0, T * B * sizeof(int64_t), st));
+  if (e->N > 0) {
+    HIPCHK(hipMemcpyAsync(d_spec, t_spec.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_pin, t_pin.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_limit, t_limit.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    const dim3 grid((unsigned)((T + ykk::kExplainTasks - 1) / ykk::kExplainTasks), (unsigned)((e->N + ykk::kBlock - 1) / ykk::kBlock));
+    hipLaunchKernelGGL(ykk::k_preempt_headroom, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e), reclaim_table(e), (int)T, d_spec,
+                       d_pin, d_limit, pre, filt, (ykk::i64*)d_cells);
+    HIPCHK(hipGetLastError());
+  }
+  if (sharded) NCCLCHK(rccl()->AllReduce(d_cells, d_cells, T * B, ncclInt64, ncclSum, e->comm, st));
+  std::vector<int64_t> rows(T * B);
+  HIPCHK(hipMemcpyAsync(rows.data(), d_cells, T * B * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  // ([27] arrives as the number of shards whose spec table does not evaluate the spec; the coupled rule is ykpred_headroom's)
+  for (int i = 0; i < n_asks; ++i) {
+    const size_t k = (size_t)task_of[(size_t)i];
+    ykfinish::preempt_headroom_finish(rows.data() + k * B, t_limit[k], wants ? wants[i] : 1, headroom_coupled(e, t_spec[k], pre, filt), out + (size_t)i * B);
+  }
+  return YKPRED_OK;
+}
+
+// rep_L of one ask on every node of this table, L = 0 .. limit (this shard's nodes on a sharded engine; nothing is exchanged)
+int32_t ykpred_preempt_headroom_pod(ykpred_engine_t* e, int32_t pod, int32_t limit, uint32_t pre, uint32_t filt, int32_t* out) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:preempt_headroom_pod");
+  if (e) e->n_queries++;
+  if (!e || !out) return fail(e, YKPRED_E_INVALID, "preempt_headroom_pod: bad argument");
+  if (!(pre & filt & YKPRED_PLUGIN_NODE_RESOURCES_FIT)) return fail(e, YKPRED_E_INVALID, "preempt_headroom_pod: NodeResourcesFit must be in both plugin lists (nothing else bounds the count)");
+  if (!e->nodes_set || !e->specs_set || !e->pods_set) return fail(e, YKPRED_E_STATE, "preempt_headroom_pod: tables not uploaded");
+  if (e->rc_tiers == 0) return fail(e, YKPRED_E_STATE, "preempt_headroom_pod: no reclaim table (ykpred_set_reclaim)");
+  if (pod < 0 || pod >= e->P) return fail(e, YKPRED_E_INVALID, "preempt_headroom_pod: index out of range");
+  if (limit < 0 || limit > e->rc_tiers) return fail(e, YKPRED_E_INVALID, "preempt_headroom_pod: limit outside 0 .. tiers");
+  if (e->N == 0) return YKPRED_OK;
+  const size_t N = (size_t)e->N, cells = (size_t)(limit + 1) * N;
+  const int32_t spec = e->h_pod_spec[(size_t)pod];
+  if (headroom_coupled(e, spec, pre, filt)) {  // no per-node figure exists for copies that interact across nodes
+    std::fill(out, out + cells, (int32_t)-1);
+    return YKPRED_OK;
+  }
+  HIPCHK(hipSetDevice(e->cfg.device));
+  hipStream_t st = e->own_stream;
+  if (e->spread_dirty) TRY(build_spread_tables(e, st));
+  HIPCHK(e->d_scratch.ensure(cells * sizeof(int32_t) + 64));
+  hipLaunchKernelGGL(ykk::k_preempt_headroom_pod, dim3((unsigned)((N + ykk::kBlock - 1) / ykk::kBlock)), dim3(ykk::kBlock), 0, st, node_table(e),
+                     spec_table(e), reclaim_table(e), spec, e->h_pod_pin[(size_t)pod], limit, pre, filt, e->d_scratch.as<int32_t>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, e->d_scratch.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   return YKPRED_OK;
 }

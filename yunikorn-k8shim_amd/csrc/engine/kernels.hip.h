@@ -3727,6 +3727,21 @@ constexpr int kReachNever = kReachMaxTiers + 1;
 // with bytes of 0x7f: a key whose level field is above kReachMaxTiers says "no node".
 constexpr int kReachLevelShift = 59, kReachPodsShift = 31;
 constexpr i64 kReachPodsMax = (1ll << 28) - 1;
+// One step of the tier walk: the np > 0 pods of `tier` leave `node` — the working copy's free values grow by the tier's request vector,
+// its port words become the tier's ports_after, *gone grows by np and the slot flag follows (slots = allowed - count + *gone).
+__device__ __forceinline__ void reclaim_tier_gone(const NodeTable& t, const ReclaimTable& rc, int tier, int node, int np, i64 count, i64 allowed,
+                                                  NodeRegs* w, i64* gone) {
+#pragma unroll
+  for (int r = 0; r < kMaxR; ++r)
+    if (r < t.R) w->fr[r] += rc.req[((size_t)tier * t.R + r) * t.n + node];
+  if (rc.ports_after) {
+#pragma unroll
+    for (int k = 0; k < kMaxKP; ++k)
+      if (k < t.KP) w->pt[k] = rc.ports_after[((size_t)tier * t.KP + k) * t.n + node];
+  }
+  *gone += np;
+  w->slots_ok = count - *gone + 1 <= allowed;
+}
 __device__ __forceinline__ int reach_level(const NodeTable& t, const SpecTable& s, const ReclaimTable& rc, int spec, int pin, int node,
                                            const NodeRegs& nr, i64 count, i64 allowed, int limit, unsigned pre_mask, unsigned filt_mask,
                                            i64* victims) {
@@ -3744,16 +3759,7 @@ __device__ __forceinline__ int reach_level(const NodeTable& t, const SpecTable& 
   for (int tier = 0; tier < limit; ++tier) {
     const int np = rc.pods[(size_t)tier * t.n + node];
     if (np == 0) continue;  // nothing leaves: the verdict of the step before stands
-#pragma unroll
-    for (int r = 0; r < kMaxR; ++r)
-      if (r < t.R) w.fr[r] += rc.req[((size_t)tier * t.R + r) * t.n + node];
-    if (rc.ports_after) {
-#pragma unroll
-      for (int k = 0; k < kMaxKP; ++k)
-        if (k < t.KP) w.pt[k] = rc.ports_after[((size_t)tier * t.KP + k) * t.n + node];
-    }
-    gone += np;
-    w.slots_ok = count - gone + 1 <= allowed;
+    reclaim_tier_gone(t, rc, tier, node, np, count, allowed, &w, &gone);
     if (eval_pair(s, spec, pin, node, w, pre_mask, filt_mask, &code, &reason)) {
       *victims = gone;
       return tier + 1;
@@ -3828,6 +3834,110 @@ __global__ __launch_bounds__(kBlock) void k_preempt_reach_pod(NodeTable t, SpecT
   i64 victims = 0;
   const int level = reach_level(t, s, rc, spec, pin, n, nr, (i64)t.count[n], (i64)t.allowed[n], limit, pre_mask, filt_mask, &victims);
   out[n] = level == kReachNever ? -1 : level;
+}
+
+// ykpred_preempt_headroom: copies of an ask per preemption level. rep_L(a, n) = replicas(a, n) on the node with all pods of tiers < L gone:
+// the tier walk of reach_level with replicas() in the place of eval_pair, on the same working copy. Nothing is indexed by the level in
+// registers: a lane keeps its last rep (`prev`) and the `gone` value at its last rise (`paid`); at a level where some lane of the wave
+// rises, the wave sums rep - prev and gone - paid, counts the lanes whose first copy arrives, and lane 0 adds the three numbers to the
+// LDS cells of that level (the level is wave-uniform). What arrives in cells[tasks][32] are PER-LEVEL DELTAS — [0..8] copies, [9..17]
+// nodes, [18..26] victim pods — which the host sums (preempt_headroom_finish.h); [27] is the `unsupported` flag. Integer adds only.
+// Skipped wave-uniformly: a tier in which no walking lane has a pod, and the whole walk of a task on which no lane can rise — a lane
+// walks unless its level-0 failure is one that no removal changes (reach_level's test).
+constexpr int kPreemptHeadroomCells = 32;
+constexpr int kPreemptHeadroomAcc = 27;  // LDS cells per task: three rows of levels 0..8
+__device__ __forceinline__ bool reach_can_open(const SpecTable& s, int spec, int pin, int node, const NodeRegs& nr, unsigned pre_mask,
+                                               unsigned filt_mask) {
+  int code = 0;
+  unsigned reason = 0;
+  if (eval_pair(s, spec, pin, node, nr, pre_mask, filt_mask, &code, &reason)) return true;
+  return code == 5 || code == 6;  // NodePorts, NodeResourcesFit: see reach_level
+}
+__global__ __launch_bounds__(kBlock) void k_preempt_headroom(NodeTable t, SpecTable s, ReclaimTable rc, int n_tasks,
+                                                             const int* __restrict__ task_spec, const int* __restrict__ task_pin,
+                                                             const int* __restrict__ task_limit, unsigned pre_mask, unsigned filt_mask,
+                                                             i64* __restrict__ cells) {
+  __shared__ i64 acc[kExplainTasks * kPreemptHeadroomAcc];
+  for (int i = threadIdx.x; i < kExplainTasks * kPreemptHeadroomAcc; i += kBlock) acc[i] = 0;
+  __syncthreads();
+  const int lane = threadIdx.x % kWave;
+  bool live;
+  const int n = headroom_node(t, &live);
+  const int k0 = blockIdx.x * kExplainTasks, kend = min(k0 + kExplainTasks, n_tasks);
+  if (__ballot(live)) {  // (wave-uniform: a wave wholly past N skips the walk, not the barriers)
+    NodeRegs nr;
+    load_node(t, n, &nr);
+    const i64 count = live ? (i64)t.count[n] : 0, allowed = live ? (i64)t.allowed[n] : 0;
+    for (int k = k0; k < kend; ++k) {
+      const int spec = task_spec[k], pin = task_pin[k], limit = task_limit[k];
+      i64* a = acc + (k - k0) * kPreemptHeadroomAcc;
+      // the wave's three numbers of one level (wave-uniform), called only where some lane rises
+      auto add_level = [&](int level, i64 copies, bool first, i64 pods) {
+#pragma unroll
+        for (int off = kWave / 2; off > 0; off >>= 1) {
+          copies += (i64)__shfl_xor((long long)copies, off, kWave);
+          pods += (i64)__shfl_xor((long long)pods, off, kWave);
+        }
+        const int nodes = __popcll(__ballot(first));
+        if (lane == 0) {
+          atomicAdd((u64*)&a[level], (u64)copies);
+          if (nodes) atomicAdd((u64*)&a[9 + level], (u64)nodes);
+          if (pods) atomicAdd((u64*)&a[18 + level], (u64)pods);
+        }
+      };
+      int binder = 0;
+      int prev = live ? replicas(s, spec, pin, n, nr, allowed - count, pre_mask, filt_mask, &binder) : 0;
+      if (__ballot(prev > 0)) add_level(0, prev, prev > 0, 0);
+      bool walks = live && limit > 0;
+      if (walks && prev == 0) walks = reach_can_open(s, spec, pin, n, nr, pre_mask, filt_mask);
+      if (!__ballot(walks)) continue;  // (wave-uniform: nothing to remove, or no lane that a removal could change)
+      NodeRegs w = nr;
+      i64 gone = 0, paid = 0;
+      for (int tier = 0; tier < limit; ++tier) {
+        const int np = walks ? rc.pods[(size_t)tier * t.n + n] : 0;
+        if (!__ballot(np != 0)) continue;  // (wave-uniform: the tier is empty on every walking lane)
+        int rep = prev;
+        if (np != 0) {
+          reclaim_tier_gone(t, rc, tier, n, np, count, allowed, &w, &gone);
+          rep = replicas(s, spec, pin, n, w, allowed - count + gone, pre_mask, filt_mask, &binder);
+        }
+        const bool rise = rep > prev;
+        if (!__ballot(rise)) continue;
+        add_level(tier + 1, rise ? (i64)rep - prev : 0, rise && prev == 0, rise ? gone - paid : 0);
+        if (rise) prev = rep, paid = gone;
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < (kend - k0) * kPreemptHeadroomAcc; i += kBlock) {
+    const i64 v = acc[i];
+    if (v) atomicAdd((u64*)&cells[(size_t)(k0 + i / kPreemptHeadroomAcc) * kPreemptHeadroomCells + i % kPreemptHeadroomAcc], (u64)v);
+  }
+  headroom_unsupported(s, k0, kend, [&](int k) { return task_spec[k]; }, cells + 27, kPreemptHeadroomCells);
+}
+
+// rep_L of ONE ask on every node of the table, L = 0 .. limit (thread = node, as k_preempt_reach_pod): out[L][n]
+__global__ __launch_bounds__(kBlock) void k_preempt_headroom_pod(NodeTable t, SpecTable s, ReclaimTable rc, int spec, int pin, int limit,
+                                                                 unsigned pre_mask, unsigned filt_mask, int* __restrict__ out) {
+  int n = blockIdx.x * kBlock + threadIdx.x;
+  if (n >= t.n) return;
+  NodeRegs nr;
+  load_node(t, n, &nr);
+  const i64 count = (i64)t.count[n], allowed = (i64)t.allowed[n];
+  int binder = 0;
+  int rep = replicas(s, spec, pin, n, nr, allowed - count, pre_mask, filt_mask, &binder);
+  out[n] = rep;
+  const bool walks = rep > 0 || reach_can_open(s, spec, pin, n, nr, pre_mask, filt_mask);
+  NodeRegs w = nr;
+  i64 gone = 0;
+  for (int tier = 0; tier < limit; ++tier) {
+    const int np = walks ? rc.pods[(size_t)tier * t.n + n] : 0;
+    if (np != 0) {
+      reclaim_tier_gone(t, rc, tier, n, np, count, allowed, &w, &gone);
+      rep = max(rep, replicas(s, spec, pin, n, w, allowed - count + gone, pre_mask, filt_mask, &binder));
+    }
+    out[(size_t)(tier + 1) * t.n + n] = rep;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -3752,6 +3752,77 @@ int32_t ykhost_preempt_reach_by_key(ykhost_t* h, const char* allocation_key, int
   return 0;
 }
 
+// ---- preemption headroom (ykpred_preempt_headroom): copies of an ask per preemption level ------------------------------------------------
+int32_t ykhost_preempt_headroom(ykhost_t* h, int32_t n, const int32_t* asks, const int64_t* wants, int64_t* out_cells) {
+  YKHOST_LOCKED(h);
+  constexpr size_t B = YKPRED_PREEMPT_HEADROOM_CELLS;
+  if (n < 0 || (n > 0 && !out_cells)) return fail(h, "preempt_headroom: bad argument", -1);
+  if (wants)
+    for (int i = 0; i < n; ++i)
+      if (wants[i] < 1) return fail(h, "preempt_headroom: want below 1", YKPRED_E_INVALID);
+  int rc = reclaim_sync(h, "preempt_headroom");
+  if (rc) return rc;
+  int32_t world = 1;
+  ykpred_comm_info(h->eng, nullptr, &world, nullptr);
+  const int P = (int)h->pending.size();
+  for (int i = 0; i < n; ++i)
+    if ((asks ? asks[i] : i) < 0 || (asks ? asks[i] : i) >= P) return fail(h, "preempt_headroom: ask index out of range", YKPRED_E_INVALID);
+  // (an ask routed to the CPU manager gets its status here; on a node-sharded handle every ask goes to the engine, as in ykhost_preempt_reach)
+  std::vector<int32_t> list, limits, slot;
+  std::vector<int64_t> want;
+  for (int i = 0; i < n; ++i) {
+    const int row = asks ? asks[i] : i;
+    const Pod* p = h->pending[(size_t)row];
+    int64_t* c = out_cells + (size_t)i * B;
+    if (world <= 1 && h->enc.unsupported.count(p->tpl)) {
+      std::fill(c, c + B, (int64_t)0);
+      c[27] = 1;
+      c[28] = reclaim_limit(h, p);
+      c[29] = wants ? wants[i] : 1;
+    } else {
+      list.push_back(row);
+      limits.push_back(reclaim_limit(h, p));
+      want.push_back(wants ? wants[i] : 1);
+      slot.push_back(i);
+    }
+  }
+  if (list.empty() && world <= 1) return 0;
+  std::vector<int64_t> rows(list.size() * B);
+  rc = ykpred_preempt_headroom(h->eng, (int32_t)list.size(), list.data(), limits.data(), want.data(), h->alloc_pre, h->alloc_filt, rows.data());
+  if (rc) return fail(h, std::string("ykpred_preempt_headroom: ") + ykpred_last_error(h->eng), rc);
+  for (size_t k = 0; k < list.size(); ++k) memcpy(out_cells + (size_t)slot[k] * B, rows.data() + k * B, B * sizeof(int64_t));
+  return 0;
+}
+
+int32_t ykhost_preempt_headroom_nodes(ykhost_t* h, int32_t pod, int32_t* out, int32_t* out_limit) {
+  YKHOST_LOCKED(h);
+  if (!out || !out_limit) return fail(h, "preempt_headroom_nodes: bad argument", -1);
+  int rc = reclaim_sync(h, "preempt_headroom_nodes");
+  if (rc) return rc;
+  if (pod < 0 || pod >= (int)h->pending.size()) return fail(h, "preempt_headroom_nodes: ask index out of range", YKPRED_E_INVALID);
+  *out_limit = reclaim_limit(h, h->pending[(size_t)pod]);
+  rc = ykpred_preempt_headroom_pod(h->eng, pod, *out_limit, h->alloc_pre, h->alloc_filt, out);
+  if (rc) return fail(h, std::string("ykpred_preempt_headroom_pod: ") + ykpred_last_error(h->eng), rc);
+  return 0;
+}
+
+// One ask named as the core names it, one crossing: the 32 cells — in front of the gang's placeholder creation.
+int32_t ykhost_preempt_headroom_by_key(ykhost_t* h, const char* allocation_key, int64_t want, int64_t* out32) {
+  YKHOST_LOCKED(h);
+  if (!out32) return fail(h, "preempt_headroom_by_key: bad argument", -1);
+  std::fill(out32, out32 + YKPRED_PREEMPT_HEADROOM_CELLS, (int64_t)0);
+  out32[29] = want;
+  out32[30] = -1;
+  if (want < 1) return fail(h, "preempt_headroom_by_key: want below 1", YKPRED_E_INVALID);
+  int32_t row = -1;
+  int rc = ask_row_by_key(h, allocation_key, &out32[27], &row);
+  if (rc) {
+    if (out32[27] == 1) out32[30] = 0;  // (a routed ask: every cell but [27..29] is 0)
+    return rc;
+  }
+  return ykhost_preempt_headroom(h, 1, &row, &want, out32);
+}
+
 // ---- headroom per topology domain (ykpred_headroom_groups) --------------------------------------------------------------------------
 // The groups of a label key: ids are the ranks of the bytewise-sorted distinct values, a node without the label gets -1. The column is
 // kept per (key, node-table epoch). On a node-sharded handle the value lists of the shards are united first (lengths, then the lists

@@ -58,6 +58,11 @@ AFFINITY_HEADROOM_CELLS = 16
 # lowest level >= 1 with a node (0: none), the best node at it (fewest victim pods, lowest index; -1: none), its victim pods, 0
 REACH_CELLS, REACH_MAX_TIERS = 16, 8
 REACH_NEVER, REACH_STATUS, REACH_LIMIT, REACH_BEST_LEVEL, REACH_BEST_NODE, REACH_BEST_PODS = 9, 10, 11, 12, 13, 14
+# ykpred_preempt_headroom: per ask int64[PREEMPT_HEADROOM_CELLS] = copies(L), nodes(L), victims(L) for L = 0..8 from the three row offsets,
+# status (0 computed, 1 routed, 2 coupled), the ask's limit, the want, the lowest level whose copies meet the want (-1: none), 0
+PREEMPT_HEADROOM_CELLS = 32
+PREEMPT_HEADROOM_COPIES, PREEMPT_HEADROOM_NODES, PREEMPT_HEADROOM_VICTIMS = 0, 9, 18
+PREEMPT_HEADROOM_STATUS, PREEMPT_HEADROOM_LIMIT, PREEMPT_HEADROOM_WANT, PREEMPT_HEADROOM_LEVEL = 27, 28, 29, 30
 
 
 def plugin_mask(names):
@@ -783,6 +788,69 @@ class GpuPredicateManager:
             raise KeyError(uid)
         self._check(rc)
         return out, buf.value.decode()
+
+    # ---- preemption headroom: copies of an ask per preemption level ------------------------------------------------------
+    def preempt_headroom(self, pods=None, wants=None, pre_mask=None, filt_mask=None):
+        """Per ask the copies the cluster takes per preemption LEVEL, reduced on the device (ykpred_preempt_headroom):
+        np.int64[n, PREEMPT_HEADROOM_CELLS] — [PREEMPT_HEADROOM_COPIES + L] the copies once every pod of tiers < min(L, limit) is gone,
+        [PREEMPT_HEADROOM_NODES + L] the nodes that take at least one, [PREEMPT_HEADROOM_VICTIMS + L] the pods of the fewest whole tiers
+        that give each node those copies, [PREEMPT_HEADROOM_STATUS] (1 routed, 2 coupled: copies and victims -1), [PREEMPT_HEADROOM_LIMIT],
+        [PREEMPT_HEADROOM_WANT], [PREEMPT_HEADROOM_LEVEL] the lowest level whose copies meet the want (-1: none). pods: ask indices or UIDs
+        in any order, repeats allowed; None = every ask. wants: one int >= 1 per listed ask; None = 1 each. Always the allocation-phase
+        lists; explicit masks go to the engine with the limits the host derives. Needs no evaluation and disturbs none."""
+        if pods is None:
+            count, ptr = self.num_pods, None
+        else:
+            idx = [p if isinstance(p, (int, np.integer)) else self.pod_index(p) for p in pods]
+            arr = np.ascontiguousarray(idx, dtype=np.int32)
+            count, ptr = len(arr), arr.ctypes.data
+        wptr = None
+        if wants is not None:
+            warr = np.ascontiguousarray(list(wants), dtype=np.int64)
+            if len(warr) != count:
+                raise ValueError("preempt_headroom: one want per listed ask")
+            wptr = warr.ctypes.data if count else None
+        out = np.zeros((max(count, 1), PREEMPT_HEADROOM_CELLS), dtype=np.int64)
+        if pre_mask is None and filt_mask is None:
+            self._check(self._L.ykhost_preempt_headroom(self._h, count, ptr, wptr, out.ctypes.data))
+        else:
+            pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
+            limits = np.zeros(max(count, 1), dtype=np.int32)
+            self._check(self._L.ykhost_preempt_limits(self._h, count, ptr, limits.ctypes.data))  # (syncs the tables and the reclaim table)
+            if ptr is None:
+                arr = np.arange(count, dtype=np.int32)
+                ptr = arr.ctypes.data
+            self._pcheck(self._P.ykpred_preempt_headroom(self.engine, count, ptr, limits.ctypes.data, wptr, pre, filt, out.ctypes.data))
+        return out[:count].copy()
+
+    def preempt_headroom_nodes(self, pod, pre_mask=None, filt_mask=None):
+        """The copies of ONE ask (index or UID) on every node per level (ykpred_preempt_headroom_pod): np.int32[limit + 1, N], row L =
+        the copies once every pod of tiers < L is gone; -1 everywhere for a coupled ask, 0 for a routed one. On a node-sharded manager:
+        this shard's nodes."""
+        p = int(pod if isinstance(pod, (int, np.integer)) else self.pod_index(pod))
+        limit = np.zeros(1, dtype=np.int32)
+        out = np.zeros((REACH_MAX_TIERS + 1) * max(self.num_nodes, 1), dtype=np.int32)
+        if pre_mask is None and filt_mask is None:
+            self._check(self._L.ykhost_preempt_headroom_nodes(self._h, p, out.ctypes.data, limit.ctypes.data))
+        else:
+            pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
+            arr = np.array([p], dtype=np.int32)
+            self._check(self._L.ykhost_preempt_limits(self._h, 1, arr.ctypes.data, limit.ctypes.data))
+            self._pcheck(self._P.ykpred_preempt_headroom_pod(self.engine, p, int(limit[0]), pre, filt, out.ctypes.data))
+        rows = int(limit[0]) + 1
+        return out[:rows * self.num_nodes].reshape(rows, self.num_nodes).copy()
+
+    def preempt_headroom_by_key(self, uid, want=1):
+        """One ask by allocation key and its want in one crossing (ykhost_preempt_headroom_by_key) → np.int64[PREEMPT_HEADROOM_CELLS].
+        Raises UnsupportedAsk for a routed ask, KeyError for an unknown pod."""
+        out = np.zeros(PREEMPT_HEADROOM_CELLS, dtype=np.int64)
+        rc = self._L.ykhost_preempt_headroom_by_key(self._h, uid.encode(), int(want), out.ctypes.data)
+        if rc == -13:
+            raise UnsupportedAsk(self._L.ykhost_last_error(self._h).decode())
+        if rc in (-10, -12):
+            raise KeyError(uid)
+        self._check(rc)
+        return out
 
     def reclaim_table(self):
         """The reclaim planes the mirror derives from the pods on its nodes (ykhost_reclaim_table; works without a device) →
