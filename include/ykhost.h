@@ -370,6 +370,40 @@ int32_t ykhost_preempt_headroom(ykhost_t* h, int32_t n, const int32_t* asks /* N
 int32_t ykhost_preempt_headroom_nodes(ykhost_t* h, int32_t pod, int32_t* out /* [limit+1][N] */, int32_t* out_limit);
 int32_t ykhost_preempt_headroom_by_key(ykhost_t* h, const char* allocation_key, int64_t want, int64_t* out32 /* [32] */);
 
+/* PREEMPTION VICTIMS (ykpred.h: ykpred_preempt_victims) — the shortest victim prefix on every node in one pass: what the core's loop of
+ * one PreemptionPredicates callback per candidate node answers, from resident state. Tiers, limits and victim eligibility are those of
+ * ykhost_set_preemption_tiers; order(n) = the pods of node n that are in a tier, sorted by (priority ascending, uid ascending
+ * bytewise); always the ALLOCATION-phase plugin lists. The mirror keeps the victim table — one segment per node with a capacity of
+ * count + count / 2 + 4 rows — and NOTHING of it is derived or uploaded before the first call of this group: at a call it patches the
+ * segments of the nodes whose pods changed (add / remove / update / assume / forget), or derives and uploads the whole table after a
+ * bounds change, an engine re-creation or a segment that outgrew its capacity.
+ *   ykhost_preempt_victims         syncs, brings the reclaim and the victim table up to date and makes ONE engine call for the listed
+ *                                  asks (NULL = asks 0..n-1): out_cells[i] = the YKPRED_VICTIM_CELLS cells. An ask routed to the CPU
+ *                                  manager gets status [3] = 1 without a device call. YKPRED_E_STATE without tiers. Collective on a
+ *                                  node-sharded handle: every rank passes the same asks.
+ *   ykhost_preempt_victims_nodes   need of ONE ask on every node (ykpred_preempt_victims_pod): 0 fits as it stands, k >= 1 the first k
+ *                                  pods of order(n) must go, -1 never; this shard's nodes on a node-sharded handle.
+ *   ykhost_victim_list             the uids of order(node) in tiers < limit, NUL-separated (each uid followed by one NUL), *count of
+ *                                  them: the first `need` of them are the victims. A buffer too short holds the uids that fit whole;
+ *                                  *count is always the full number. Works on a mirror-only handle.
+ *   ykhost_preempt_victims_by_key  ONE crossing for one ask by allocation key (pod UID): the cells, the best node ([6]) by NAME and the
+ *                                  uids of its prefix of [7] pods, NUL-separated ("" / nothing when there is none, or when the node
+ *                                  lies on another shard). → 0, or the errors of ykhost_headroom_by_key (YKHOST_E_UNSUPPORTED with
+ *                                  out16[3] = 1).
+ *   ykhost_victim_table            the table as the mirror keeps it (patched, not derived afresh), copied out: dims = { T, R, KP, N, P };
+ *                                  seg_base [N], seg_cap [N], tier_end [T][N], cum [R][P], ports_after [KP][P] (any NULL: only the
+ *                                  dims come back). Works on a mirror-only handle: the table and its patching can be checked without a
+ *                                  device.
+ *   ykhost_victim_stats            out2 = { whole tables derived, segments patched } so far. */
+int32_t ykhost_preempt_victims(ykhost_t* h, int32_t n, const int32_t* asks /* NULL = asks 0..n-1 */, int64_t* out_cells /* [n][16] */);
+int32_t ykhost_preempt_victims_nodes(ykhost_t* h, int32_t pod, int32_t* out /* [N] */);
+int32_t ykhost_victim_list(ykhost_t* h, int32_t node, int32_t limit, char* uids_buf, int64_t len, int32_t* count);
+int32_t ykhost_preempt_victims_by_key(ykhost_t* h, const char* allocation_key, int64_t* out16 /* [16] */, char* best_node_name, int64_t name_len,
+                                      char* victim_uids, int64_t uids_len);
+int32_t ykhost_victim_table(ykhost_t* h, int32_t* dims /* [5] */, int32_t* seg_base, int32_t* seg_cap, int32_t* tier_end, int64_t* cum,
+                            uint64_t* ports_after);
+int32_t ykhost_victim_stats(ykhost_t* h, int64_t* out2 /* [2] */);
+
 /* Engine calls that came back YKPRED_E_DEVICE / YKPRED_E_NOMEM so far (failed allocation, lost device). Each one marks the whole
  * device state stale: the failing call returns its error (Predicates() < 0: the Go manager routes the ask to the CPU predicate
  * manager — SURVEY.md §5, "must degrade, never fail scheduling"), the mirror stays intact, and the next ykhost_sync /

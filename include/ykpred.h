@@ -38,7 +38,9 @@
 extern "C" {
 #endif
 
-/* (ykpred_preempt_headroom + ykpred_preempt_headroom_pod + YKPRED_PREEMPT_HEADROOM_CELLS arrived WITHIN version 4 too:
+/* (ykpred_preempt_victims + ykpred_preempt_victims_pod + ykpred_set_victims + ykpred_update_victims_node + YKPRED_VICTIM_CELLS arrived
+ *    WITHIN version 4 too: dlsym("ykpred_preempt_victims"))
+ * (ykpred_preempt_headroom + ykpred_preempt_headroom_pod + YKPRED_PREEMPT_HEADROOM_CELLS arrived WITHIN version 4 too:
  *    dlsym("ykpred_preempt_headroom"))
  * (ykpred_preempt_reach + ykpred_preempt_reach_pod + ykpred_set_reclaim + ykpred_update_reclaim_node + YKPRED_REACH_CELLS arrived
  *    WITHIN version 4 too: dlsym("ykpred_preempt_reach"))
@@ -772,6 +774,63 @@ int32_t ykpred_preempt_headroom(ykpred_engine_t* e, int32_t n_asks, const int32_
  * YKPRED_SPEC_UNSUPPORTED spec. This shard's nodes only on a sharded engine. */
 int32_t ykpred_preempt_headroom_pod(ykpred_engine_t* e, int32_t pod_index, int32_t limit, uint32_t prefilter_plugins, uint32_t filter_plugins,
                                     int32_t* out /* [limit+1][N] */);
+
+/* PREEMPTION VICTIMS — the shortest victim prefix on every node in one pass: what one PreemptionPredicates call per
+ * candidate node answers, from resident state.
+ *
+ * The VICTIM TABLE is resident beside the reclaim table and shard-local on the node axis: one row per eligible pod (a pod in a tier,
+ * as the reclaim table defines it), one contiguous SEGMENT per node holding order(n) = the node's eligible pods sorted by (priority
+ * ascending, uid ascending bytewise). Tiers are monotone in priority, so the pods of tiers < L are a prefix of the segment for every L. */
+typedef struct ykpred_victims {
+  int32_t tiers;               /* T: the tier count of the resident reclaim table */
+  int64_t rows;                /* P: rows of the two row planes, < 2^31; the segments lie inside 0..P */
+  const int32_t* seg_base;     /* [N] first row of the node's segment */
+  const int32_t* seg_cap;      /* [N] rows the segment may grow to (>= the node's victim count; the slack rows are never read) */
+  const int32_t* tier_end;     /* [T][N] victims of the node in tiers <= t: non-decreasing in t, tier_end[T-1] <= seg_cap */
+  const int64_t* cum;          /* [R][P] PREFIX sums of the request vectors within the segment: row p = victims 0..p of its node */
+  const uint64_t* ports_after; /* [KP][P] the node's port_bits once victims 0..p are gone; NULL = no victim holds a dictionary port
+                                  or KP == 0 */
+} ykpred_victims_t;
+/* Uploads the table for the current node table. NULL drops it; a ykpred_set_nodes that changes N drops it as well. YKPRED_E_STATE
+ * without a node table or without a reclaim table of the same T; YKPRED_E_INVALID for a segment outside 0..P or a tier_end column that
+ * descends or passes its capacity. No other call reads the table, and setting it invalidates no evaluation. */
+int32_t ykpred_set_victims(ykpred_engine_t* e, const ykpred_victims_t* table);
+/* Rewrites ONE node's segment and its tier_end column in place: `one` holds tier_end [T], cum [R][count] and ports_after [KP][count]
+ * (given exactly when the resident table has that plane; seg_base, seg_cap and rows are not read). count > seg_cap[node_index] is
+ * YKPRED_E_INVALID with nothing written: the caller knows the capacities and uploads the whole table instead. */
+int32_t ykpred_update_victims_node(ykpred_engine_t* e, int32_t node_index, int32_t count, const ykpred_victims_t* one);
+
+/* need(a, n): 0 when Predicates(a, n) fits as the node stands; otherwise k >= 1 with k - 1 == ykpred_preemption(a, n, victims(a, n),
+ * start 0), victims(a, n) = the first tier_end[limit-1][n] rows of the segment; -1 when that call returns -1 or a PreFilter plugin
+ * rejects the pair. "fits with victims 0..i gone" is monotone in i (§4.16's argument per victim), so need is found by BISECTION:
+ * at most ceil(log2 len) gathers of one table row. Where need >= 1: tier(order(n)[need-1]) + 1 == ykpred_preempt_reach_pod, and need <=
+ * the whole-tier pod count reach reports. */
+#define YKPRED_VICTIM_CELLS 16
+/* per ask, int64[16], over all nodes of the table:
+ *  [0]      nodes with need 0
+ *  [1]      nodes with need >= 1
+ *  [2]      nodes with need -1
+ *  [3]      status: 0 computed; 1 the ask's spec is YKPRED_SPEC_UNSUPPORTED (every other cell 0 except [4], [6] == -1)
+ *  [4]      the limit, echoed
+ *  [5]      the level of the BEST node — lowest level, then fewest victims, then lowest index —, 0 when there is none
+ *  [6]      the best node (a GLOBAL index on a sharded engine), -1 when there is none
+ *  [7]      the best node's need (saturating at 2^28 - 1)
+ *  [8]      the sum of need over the nodes of [1]
+ *  [9..15]  0
+ * Invariant at status 0: [0] + [1] + [2] == N.
+ * Everything else is ykpred_preempt_reach's: tasks = the distinct (spec, NodeName, limit); the call reads the TABLES only, needs no
+ *   evaluation and invalidates none; it prepares the topology histograms as ykpred_query does; one query; roctx range
+ *   "ykpred:preempt_victims"; YKPRED_E_STATE without a victim table (or when the reclaim table's T no longer matches);
+ *   YKPRED_E_INVALID for a limit outside 0..T.
+ * NODE-SHARDED engines: COLLECTIVE — the agreement all-gather first (it covers the limits), then one all-reduce SUM (int64) of the cells
+ *   and one all-reduce MIN (int64) of the packed best keys (ykpred_preempt_reach's key with the exact need in the victim field). */
+int32_t ykpred_preempt_victims(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks /* host, ask indices, any order, repeats allowed */,
+                               const int32_t* limits /* host, [n_asks], 0..T */, uint32_t prefilter_plugins, uint32_t filter_plugins,
+                               int64_t* out /* host, [n_asks][YKPRED_VICTIM_CELLS] */);
+/* need(pod, n) for every node n of the table (thread = node). -1 everywhere for a YKPRED_SPEC_UNSUPPORTED spec. This shard's nodes only
+ * on a sharded engine. */
+int32_t ykpred_preempt_victims_pod(ykpred_engine_t* e, int32_t pod_index, int32_t limit, uint32_t prefilter_plugins, uint32_t filter_plugins,
+                                   int32_t* out /* [N] */);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Multi-GPU: node-axis shards. One engine per GPU / process holds a contiguous shard of the node table and

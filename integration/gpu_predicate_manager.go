@@ -677,6 +677,57 @@ func (m *gpuPredicateManager) PreemptionHeadroom(allocationKey string, want int6
 	}
 }
 
+// PreemptionVictims answers the core's loop of one PreemptionPredicates callback per candidate node from resident state: how many nodes
+// take the ask as they stand, how many once a prefix of their lower-priority pods — in (priority, uid) order — is gone, how many never,
+// the node that needs the shortest prefix at the lowest tier, and the uids of that prefix. The call site is in front of the core's
+// per-node predicate checks of a preemption attempt (the walk that ends in IsPodFitNodeViaPreemption, context.go:718-742): with
+// reachable == 0 the walk is skipped; otherwise bestNode with victims is the candidate to start from, and need of any other node comes
+// from ykhost_preempt_victims_nodes. ONE crossing: ykhost_preempt_victims_by_key looks the ask up by allocation key and hands the node
+// back by name and the victims by uid. ok == false when the pod is not a mirrored ask, is routed to the CPU predicate manager, no tiers
+// are set or the engine failed: the caller walks every node as before.
+func (m *gpuPredicateManager) PreemptionVictims(pod *v1.Pod) (fits, reachable, never int64, bestLevel int, bestNode string, victims []string, ok bool) {
+	if pod == nil {
+		return 0, 0, 0, 0, "", nil, false
+	}
+	var cells [16]C.int64_t
+	var best [256]C.char
+	const uidsLen = 1 << 16
+	uids := (*C.char)(C.malloc(uidsLen))
+	defer C.free(unsafe.Pointer(uids))
+	uid := C.CString(string(pod.UID))
+	rc := C.ykhost_preempt_victims_by_key(m.host, uid, &cells[0], &best[0], 256, uids, uidsLen)
+	C.free(unsafe.Pointer(uid))
+	switch {
+	case rc == 0 && cells[3] == 0:
+		bestNode = C.GoString(&best[0])
+		if bestNode != "" {
+			at := uids
+			for i := int64(0); i < int64(cells[7]); i++ {
+				v := C.GoString(at)
+				if v == "" {
+					break
+				}
+				victims = append(victims, v)
+				at = (*C.char)(unsafe.Add(unsafe.Pointer(at), len(v)+1))
+			}
+		}
+		return int64(cells[0]), int64(cells[1]), int64(cells[2]), int(cells[5]), bestNode, victims, true
+	case rc == 0:
+		return 0, 0, 0, 0, "", nil, false
+	case rc == C.YKHOST_E_UNSUPPORTED:
+		m.Counters.RoutedUnsupported.Add(1)
+		return 0, 0, 0, 0, "", nil, false
+	case rc == C.YKHOST_E_POD_NOT_FOUND || rc == C.YKHOST_E_NOT_AN_ASK:
+		m.Counters.RoutedNotMirrored.Add(1)
+		return 0, 0, 0, 0, "", nil, false
+	default:
+		m.Counters.RoutedOnError.Add(1)
+		log.Log(log.ShimPredicates).Warn("GPU predicate engine error, no preemption victims for the ask",
+			zap.String("error", C.GoString(C.ykhost_last_error(m.host))))
+		return 0, 0, 0, 0, "", nil, false
+	}
+}
+
 // ResidentStats: Predicates() calls answered from the mirrored resident answer, per pair because the node's column changed,
 // by whole-ask device queries, and the answer / failing-plugin fetches behind them.
 func (m *gpuPredicateManager) ResidentStats() (resident, dirtyColumn, query, answerFetches, codeFetches int64) {

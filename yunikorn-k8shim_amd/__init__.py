@@ -12,6 +12,8 @@ from .predicate_manager import (ALL_PLUGINS, EXPLAIN_BINS, EXPLAIN_FIT, EXPLAIN_
                                 REACH_BEST_LEVEL, REACH_BEST_NODE, REACH_BEST_PODS, REACH_CELLS, REACH_LIMIT, REACH_MAX_TIERS, REACH_NEVER, REACH_STATUS,
                                 PREEMPT_HEADROOM_CELLS, PREEMPT_HEADROOM_COPIES, PREEMPT_HEADROOM_LEVEL, PREEMPT_HEADROOM_LIMIT, PREEMPT_HEADROOM_NODES,
                                 PREEMPT_HEADROOM_STATUS, PREEMPT_HEADROOM_VICTIMS, PREEMPT_HEADROOM_WANT,
+                                VICTIM_BEST_LEVEL, VICTIM_BEST_NEED, VICTIM_BEST_NODE, VICTIM_CELLS, VICTIM_FIT, VICTIM_LIMIT, VICTIM_NEVER, VICTIM_OPEN,
+                                VICTIM_STATUS, VICTIM_TOTAL,
                                 GpuPredicateManager,
                                 PredicateError, UnsupportedAsk, plugin_mask)
 

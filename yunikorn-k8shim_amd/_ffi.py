@@ -50,6 +50,11 @@ class YkpredReclaim(C.Structure):
     _fields_ = [("tiers", C.c_int32), ("requests", C.c_void_p), ("pods", C.c_void_p), ("ports_after", C.c_void_p)]
 
 
+class YkpredVictims(C.Structure):
+    _fields_ = [("tiers", C.c_int32), ("rows", C.c_int64), ("seg_base", C.c_void_p), ("seg_cap", C.c_void_p), ("tier_end", C.c_void_p),
+                ("cum", C.c_void_p), ("ports_after", C.c_void_p)]
+
+
 MAX_TIMED = 24
 
 
@@ -153,6 +158,10 @@ def load_ykpred():
     L.ykpred_update_reclaim_node.argtypes = [C.c_void_p, C.c_int32, C.POINTER(YkpredReclaim)]
     L.ykpred_preempt_reach.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     L.ykpred_preempt_reach_pod.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.ykpred_set_victims.argtypes = [C.c_void_p, C.POINTER(YkpredVictims)]
+    L.ykpred_update_victims_node.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(YkpredVictims)]
+    L.ykpred_preempt_victims.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.ykpred_preempt_victims_pod.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
     L.ykpred_preempt_headroom.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     L.ykpred_preempt_headroom_pod.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
     _pred = L
@@ -248,6 +257,12 @@ def load_ykhost():
     L.ykhost_preempt_reach_by_key.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_char_p, C.c_int64]
     L.ykhost_preempt_limits.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.ykhost_reclaim_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ykhost_preempt_victims.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.ykhost_preempt_victims_nodes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    L.ykhost_victim_list.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+    L.ykhost_preempt_victims_by_key.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_int64]
+    L.ykhost_victim_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ykhost_victim_stats.argtypes = [C.c_void_p, C.c_void_p]
     L.ykhost_preempt_headroom.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ykhost_preempt_headroom_nodes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.ykhost_preempt_headroom_by_key.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p]

@@ -285,6 +285,13 @@ struct ykpred_engine {
   DevBuf d_rc_req, d_rc_pods, d_rc_ports;  // [T][R][N] i64; [T][N] int; [T][KP][N] u64 (only with rc_ports)
   int rc_tiers = 0;                        // 0 = no table
   bool rc_ports = false;
+  DevBuf d_victims;  // ykpred_preempt_victims: [tasks][YKPRED_VICTIM_CELLS] cells | [tasks] best keys | task specs | task pins | task limits
+  // the resident victim table (ykpred_set_victims): one row per eligible pod, one segment per node in (priority, uid) order
+  DevBuf d_vt_base, d_vt_tier_end, d_vt_cum, d_vt_ports;  // [N] int; [T][N] int; [R][P] i64; [KP][P] u64 (only with vt_ports)
+  std::vector<int32_t> h_vt_base, h_vt_cap;               // the segments, kept for ykpred_update_victims_node
+  int vt_tiers = 0;                                       // 0 = no table
+  size_t vt_rows = 0;
+  bool vt_ports = false;
   DevBuf d_bytes_gather;  // ykpred_comm_allgather_bytes
   DevBuf d_topo_agree;  // node-sharded: the shape of every rank's topology histograms (agree_topology)
   u64 dict_digest = 0;  // ykpred_set_dictionary_digest
@@ -1782,7 +1789,8 @@ void ykpred_destroy(ykpred_engine_t* e) {
                     &e->d_member_key, &e->d_name_rank, &e->d_member_tie, &e->d_class_rows_all, &e->d_gathered_classes, &e->d_class_rows_slot,
                     &e->d_class_sig_ident, &e->d_expand_count, &e->d_layout_hash, &e->d_gathered_pod_class, &e->d_row_pod,
                     &e->d_round, &e->d_fx_off, &e->d_fx_cls, &e->d_fx_cnt, &e->d_fx_occ, &e->d_sp_sig_of, &e->d_class_list_b, &e->d_gathered, &e->d_gathered_map,
-                    &e->d_xkey, &e->d_xcand, &e->d_reach, &e->d_rc_req, &e->d_rc_pods, &e->d_rc_ports})
+                    &e->d_xkey, &e->d_xcand, &e->d_reach, &e->d_rc_req, &e->d_rc_pods, &e->d_rc_ports, &e->d_victims,
+                    &e->d_vt_base, &e->d_vt_tier_end, &e->d_vt_cum, &e->d_vt_ports})
     b->release();
   if (e->ev_ready)
     for (auto& ev : e->ev) (void)hipEventDestroy(ev);
@@ -1851,6 +1859,7 @@ int32_t ykpred_set_nodes(ykpred_engine_t* e, const ykpred_nodes_t* n) {
     e->base_canon.release();
     e->base_ranked.release();
     e->rc_tiers = 0;  // the reclaim table describes N nodes
+    e->vt_tiers = 0;  // and so does the victim table
   }
   e->N = n->count;
   e->row_words = (e->N + 63) / 64;
@@ -5012,6 +5021,197 @@ int32_t ykpred_preempt_headroom_pod(ykpred_engine_t* e, int32_t pod, int32_t lim
                      spec_table(e), reclaim_table(e), spec, e->h_pod_pin[(size_t)pod], limit, pre, filt, e->d_scratch.as<int32_t>());
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, e->d_scratch.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return YKPRED_OK;
+}
+
+// The resident victim table of ykpred_preempt_victims: one row per eligible pod, one segment per node, beside the reclaim table and
+// shard-local like it. Nothing else reads it, so neither call touches the evaluation state. Everything the kernel indexes with is
+// checked HERE, against the host's copy of the segments: the kernel itself reads rows base .. base + tier_end - 1 unchecked.
+static const char* victims_column_ok(int T, const int32_t* tier_end, size_t stride, int64_t cap) {
+  int32_t prev = 0;
+  for (int t = 0; t < T; ++t) {
+    const int32_t v = tier_end[(size_t)t * stride];
+    if (v < prev) return "tier_end must not descend (and starts at >= 0)";
+    prev = v;
+  }
+  return prev > cap ? "tier_end passes the segment's capacity" : nullptr;
+}
+int32_t ykpred_set_victims(ykpred_engine_t* e, const ykpred_victims_t* vt) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:upload_victims");
+  if (!e) return YKPRED_E_INVALID;
+  e->n_uploads++;
+  if (!vt) {
+    e->vt_tiers = 0;
+    return YKPRED_OK;
+  }
+  if (!e->nodes_set) return fail(e, YKPRED_E_STATE, "set_victims: no node table");
+  if (e->rc_tiers == 0 || vt->tiers != e->rc_tiers) return fail(e, YKPRED_E_STATE, "set_victims: needs a reclaim table with the same tier count (ykpred_set_reclaim)");
+  if (vt->rows < 0 || vt->rows >= (1ll << 31)) return fail(e, YKPRED_E_INVALID, "set_victims: rows must be 0 .. 2^31 - 1");
+  if (e->N > 0 && (!vt->seg_base || !vt->seg_cap || !vt->tier_end)) return fail(e, YKPRED_E_INVALID, "set_victims: null plane");
+  if (vt->rows > 0 && !vt->cum) return fail(e, YKPRED_E_INVALID, "set_victims: null plane");
+  const size_t N = (size_t)e->N, T = (size_t)vt->tiers, P = (size_t)vt->rows;
+  for (size_t n = 0; n < N; ++n) {
+    if (vt->seg_base[n] < 0 || vt->seg_cap[n] < 0 || (int64_t)vt->seg_base[n] + vt->seg_cap[n] > vt->rows)
+      return fail(e, YKPRED_E_INVALID, "set_victims: a segment lies outside 0 .. rows");
+    if (const char* why = victims_column_ok((int)T, vt->tier_end + n, N, vt->seg_cap[n])) return fail(e, YKPRED_E_INVALID, std::string("set_victims: ") + why);
+  }
+  HIPCHK(hipSetDevice(e->cfg.device));
+  hipStream_t st = e->own_stream;
+  e->vt_tiers = 0;
+  TRY(upload(e, e->d_vt_base, vt->seg_base, N, st));
+  TRY(upload(e, e->d_vt_tier_end, vt->tier_end, T * N, st));
+  if (P > 0) TRY(upload(e, e->d_vt_cum, vt->cum, (size_t)e->R * P, st));
+  const bool ports = vt->ports_after && e->KP > 0 && P > 0;
+  if (ports) TRY(upload(e, e->d_vt_ports, vt->ports_after, (size_t)e->KP * P, st));
+  HIPCHK(hipStreamSynchronize(st));
+  e->h_vt_base.assign(vt->seg_base, vt->seg_base + N);
+  e->h_vt_cap.assign(vt->seg_cap, vt->seg_cap + N);
+  e->vt_rows = P;
+  e->vt_ports = ports;
+  e->vt_tiers = vt->tiers;
+  return YKPRED_OK;
+}
+
+int32_t ykpred_update_victims_node(ykpred_engine_t* e, int32_t idx, int32_t count, const ykpred_victims_t* one) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:update_victims_node");
+  if (!e || !one || !one->tier_end || count < 0 || (count > 0 && !one->cum)) return fail(e, YKPRED_E_INVALID, "update_victims_node: bad argument");
+  e->n_uploads++;
+  if (!e->nodes_set || e->vt_tiers == 0) return fail(e, YKPRED_E_STATE, "update_victims_node: no victim table");
+  if (idx < 0 || idx >= e->N) return fail(e, YKPRED_E_INVALID, "update_victims_node: index out of range");
+  if (one->tiers != e->vt_tiers) return fail(e, YKPRED_E_INVALID, "update_victims_node: tier count differs from the resident table");
+  if (count > e->h_vt_cap[(size_t)idx]) return fail(e, YKPRED_E_INVALID, "update_victims_node: count passes the segment's capacity — re-upload the table");
+  if (const char* why = victims_column_ok(e->vt_tiers, one->tier_end, 1, count)) return fail(e, YKPRED_E_INVALID, std::string("update_victims_node: ") + why);
+  // (a resident table without the port plane took every port word from the node table: a segment that now frees a dictionary port
+  // needs the plane, i.e. the whole table again)
+  if (count > 0 && e->KP > 0 && e->vt_ports != (one->ports_after != nullptr))
+    return fail(e, YKPRED_E_INVALID, "update_victims_node: ports_after must be given exactly when the resident table has the plane — re-upload the table");
+  HIPCHK(hipSetDevice(e->cfg.device));
+  hipStream_t st = e->own_stream;
+  const size_t N = (size_t)e->N, P = e->vt_rows, base = (size_t)e->h_vt_base[(size_t)idx], c = (size_t)count;
+  for (int t = 0; t < e->vt_tiers; ++t)
+    HIPCHK(hipMemcpyAsync(e->d_vt_tier_end.as<int>() + (size_t)t * N + idx, one->tier_end + t, sizeof(int), hipMemcpyHostToDevice, st));
+  if (c > 0) {
+    for (int r = 0; r < e->R; ++r)
+      HIPCHK(hipMemcpyAsync(e->d_vt_cum.as<i64>() + (size_t)r * P + base, one->cum + (size_t)r * c, c * sizeof(i64), hipMemcpyHostToDevice, st));
+    if (e->vt_ports)
+      for (int k = 0; k < e->KP; ++k)
+        HIPCHK(hipMemcpyAsync(e->d_vt_ports.as<u64>() + (size_t)k * P + base, one->ports_after + (size_t)k * c, c * sizeof(u64), hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  return YKPRED_OK;
+}
+
+static ykk::VictimTable victim_table(ykpred_engine* e) {
+  ykk::VictimTable vt;
+  vt.T = e->vt_tiers;
+  vt.rows = e->vt_rows;
+  vt.seg_base = e->d_vt_base.as<int>();
+  vt.tier_end = e->d_vt_tier_end.as<int>();
+  vt.cum = e->d_vt_cum.as<ykk::i64>();
+  vt.ports_after = e->vt_ports ? e->d_vt_ports.as<ykk::u64>() : nullptr;
+  return vt;
+}
+
+// The shortest victim prefix on every node: per listed (ask, limit) the need of every node reduced on the device (k_preempt_victims).
+// ykpred_preempt_reach's shape throughout — tasks, agreement, a SUM reduce of the cells, a MIN of the packed best keys.
+int32_t ykpred_preempt_victims(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, const int32_t* limits, uint32_t pre, uint32_t filt, int64_t* out) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:preempt_victims");
+  if (e) e->n_queries++;
+  static_assert(ykk::kVictimCells == YKPRED_VICTIM_CELLS, "k_preempt_victims writes the layout of ykpred.h");
+  constexpr size_t B = YKPRED_VICTIM_CELLS;
+  if (!e) return YKPRED_E_INVALID;
+  const bool args_ok = n_asks <= 0 || (asks && limits && out);
+  auto more_checks = [&](std::string* why) -> int {
+    if (e->vt_tiers == 0 || e->vt_tiers != e->rc_tiers) return *why = "preempt_victims: no victim table (ykpred_set_victims)", YKPRED_E_STATE;
+    for (int i = 0; i < n_asks; ++i)
+      if (limits[i] < 0 || limits[i] > e->vt_tiers) return *why = "preempt_victims: limit outside 0 .. tiers", YKPRED_E_INVALID;
+    return YKPRED_OK;
+  };
+  u64 more = tune_hash({(u64)(uint32_t)e->vt_tiers, 0x76696374ull});
+  if (n_asks > 0 && args_ok)
+    for (int i = 0; i < n_asks; ++i) more = tune_hash({(u64)(uint32_t)limits[i]}, more);
+  HeadroomTasks tasks;
+  tasks.extra = args_ok && n_asks > 0 ? limits : nullptr;
+  tasks.need_fit = false;
+  tasks.other_causes = "bad argument, no victim table, a limit outside 0 .. tiers, tables not uploaded, an index out of range or stale topology histograms";
+  bool run = false;
+  const int32_t rc = headroom_prepare(e, "preempt_victims", n_asks, asks, args_ok, pre, filt, more_checks, more, &tasks, &run);
+  if (!run) return rc;
+  const bool sharded = e->comm && e->comm_world > 1;
+  const std::vector<int32_t>&task_of = tasks.task_of, &t_spec = tasks.spec, &t_pin = tasks.pin, &t_limit = tasks.extra_of;
+  hipStream_t st = e->own_stream;
+  const size_t T = t_spec.size();
+  HIPCHK(e->d_victims.ensure(T * ((B + 1) * sizeof(int64_t) + 3 * sizeof(int32_t)) + 64));
+  int64_t* d_cells = e->d_victims.as<int64_t>();  // (the table and the keys first: what the reduces and the copy move)
+  int64_t* d_best = d_cells + T * B;
+  int32_t* d_spec = (int32_t*)(d_best + T);
+  int32_t* d_pin = d_spec + T;
+  int32_t* d_limit = d_pin + T;
+  HIPCHK(hipMemsetAsync(d_cells, 0, T * B * sizeof(int64_t), st));
+  HIPCHK(hipMemsetAsync(d_best, 0x7f, T * sizeof(int64_t), st));  // (level field 15: no node)
+  if (e->N > 0) {
+    HIPCHK(hipMemcpyAsync(d_spec, t_spec.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_pin, t_pin.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_limit, t_limit.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    const dim3 grid((unsigned)((T + ykk::kExplainTasks - 1) / ykk::kExplainTasks), (unsigned)((e->N + ykk::kBlock - 1) / ykk::kBlock));
+    hipLaunchKernelGGL(ykk::k_preempt_victims, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e), victim_table(e), (int)T, d_spec, d_pin,
+                       d_limit, sharded ? e->node_offset : 0, pre, filt, (ykk::i64*)d_cells, (ykk::u64*)d_best);
+    HIPCHK(hipGetLastError());
+  }
+  if (sharded) {
+    NCCLCHK(rccl()->AllReduce(d_cells, d_cells, T * B, ncclInt64, ncclSum, e->comm, st));
+    NCCLCHK(rccl()->AllReduce(d_best, d_best, T, ncclInt64, ncclMin, e->comm, st));
+  }
+  std::vector<int64_t> rows(T * (B + 1));
+  HIPCHK(hipMemcpyAsync(rows.data(), d_cells, T * (B + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  // The status per task, decided here: [3] arrives as the number of shards whose spec table does not evaluate the spec.
+  for (size_t k = 0; k < T; ++k) {
+    int64_t* row = rows.data() + k * B;
+    const u64 key = (u64)rows[T * B + k];
+    const int64_t level = (int64_t)(key >> ykk::kReachLevelShift);
+    if (row[3] != 0) {
+      std::fill(row, row + B, (int64_t)0);
+      row[3] = 1;
+      row[6] = -1;
+    } else if (level >= 1 && level <= YKPRED_REACH_MAX_TIERS) {
+      row[5] = level;
+      row[6] = (int64_t)(key & 0x7fffffffull);
+      row[7] = (int64_t)((key >> ykk::kReachPodsShift) & (u64)ykk::kReachPodsMax);
+    } else {
+      row[6] = -1;
+    }
+    row[4] = t_limit[k];
+  }
+  for (int i = 0; i < n_asks; ++i) memcpy(out + (size_t)i * B, rows.data() + (size_t)task_of[(size_t)i] * B, B * sizeof(int64_t));
+  return YKPRED_OK;
+}
+
+// need of one ask on every node of this table (this shard's nodes on a sharded engine; nothing is exchanged)
+int32_t ykpred_preempt_victims_pod(ykpred_engine_t* e, int32_t pod, int32_t limit, uint32_t pre, uint32_t filt, int32_t* out) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:preempt_victims_pod");
+  if (e) e->n_queries++;
+  if (!e || !out) return fail(e, YKPRED_E_INVALID, "preempt_victims_pod: bad argument");
+  if (!e->nodes_set || !e->specs_set || !e->pods_set) return fail(e, YKPRED_E_STATE, "preempt_victims_pod: tables not uploaded");
+  if (e->vt_tiers == 0 || e->vt_tiers != e->rc_tiers) return fail(e, YKPRED_E_STATE, "preempt_victims_pod: no victim table (ykpred_set_victims)");
+  if (pod < 0 || pod >= e->P) return fail(e, YKPRED_E_INVALID, "preempt_victims_pod: index out of range");
+  if (limit < 0 || limit > e->vt_tiers) return fail(e, YKPRED_E_INVALID, "preempt_victims_pod: limit outside 0 .. tiers");
+  if (e->N == 0) return YKPRED_OK;
+  HIPCHK(hipSetDevice(e->cfg.device));
+  hipStream_t st = e->own_stream;
+  if ((pre & filt & (YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD | YKPRED_PLUGIN_INTER_POD_AFFINITY))) TRY(ensure_histograms(e, st));
+  else if (e->spread_dirty) TRY(build_spread_tables(e, st));
+  const size_t N = (size_t)e->N;
+  HIPCHK(e->d_scratch.ensure(N * sizeof(int32_t) + 64));
+  hipLaunchKernelGGL(ykk::k_preempt_victims_pod, dim3((unsigned)((N + ykk::kBlock - 1) / ykk::kBlock)), dim3(ykk::kBlock), 0, st, node_table(e),
+                     spec_table(e), victim_table(e), e->h_pod_spec[(size_t)pod], e->h_pod_pin[(size_t)pod], limit, pre, filt, e->d_scratch.as<int32_t>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, e->d_scratch.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   return YKPRED_OK;
 }

@@ -3846,12 +3846,14 @@ __global__ __launch_bounds__(kBlock) void k_preempt_reach_pod(NodeTable t, SpecT
 // walks unless its level-0 failure is one that no removal changes (reach_level's test).
 constexpr int kPreemptHeadroomCells = 32;
 constexpr int kPreemptHeadroomAcc = 27;  // LDS cells per task: three rows of levels 0..8
+// the first failure of a pair that does not fit as the node stands: can a removal change it? NodePorts, NodeResourcesFit: see reach_level
+__device__ __forceinline__ bool reach_code_opens(int code) { return code == 5 || code == 6; }
 __device__ __forceinline__ bool reach_can_open(const SpecTable& s, int spec, int pin, int node, const NodeRegs& nr, unsigned pre_mask,
                                                unsigned filt_mask) {
   int code = 0;
   unsigned reason = 0;
   if (eval_pair(s, spec, pin, node, nr, pre_mask, filt_mask, &code, &reason)) return true;
-  return code == 5 || code == 6;  // NodePorts, NodeResourcesFit: see reach_level
+  return reach_code_opens(code);
 }
 __global__ __launch_bounds__(kBlock) void k_preempt_headroom(NodeTable t, SpecTable s, ReclaimTable rc, int n_tasks,
                                                              const int* __restrict__ task_spec, const int* __restrict__ task_pin,
@@ -3938,6 +3940,151 @@ __global__ __launch_bounds__(kBlock) void k_preempt_headroom_pod(NodeTable t, Sp
     }
     out[(size_t)(tier + 1) * t.n + n] = rep;
   }
+}
+
+// ykpred_preempt_victims: the shortest victim prefix on every node. The resident VICTIM TABLE holds one row per eligible pod, one
+// contiguous segment per node in order(n) = (priority, uid) ascending; row p carries the PREFIX sum of the request vectors of victims
+// 0..p of its node and the node's host-port words once they are gone, so the node with its first k victims removed is ONE row away:
+// free + cum[base + k - 1], slot flag from count - k, port words from ports_after[base + k - 1]. "fits with k victims gone" is monotone
+// in k, so need is found by bisection over (0, len], len = tier_end[limit - 1][n].
+// The gather is what this costs: unlike the reclaim columns, which lane = node reads coalesced, the rows of a wave's 64 nodes lie
+// base[n] apart — one step reads R + KP scattered 8-byte words per lane, each its own 64-byte sector unless the segments are short
+// enough for neighbours to share one.
+struct VictimTable {
+  int T;
+  size_t rows;             // P
+  const int* seg_base;     // [n]
+  const int* tier_end;     // [T][n] victims of the node in tiers <= t
+  const i64* cum;          // [R][P]
+  const u64* ports_after;  // [KP][P], null: no victim holds a dictionary port
+};
+constexpr int kVictimCells = 16;
+constexpr int kVictimAcc = 4;  // LDS counters per task: need 0, need >= 1, never (the sum of need and the best key sit beside them)
+// the node registers with victims 0..k-1 gone (k >= 1, row = base + k - 1), into the working copy *w
+__device__ __forceinline__ void victim_state(const NodeTable& t, const VictimTable& vt, const NodeRegs& nr, size_t row, i64 count, i64 allowed,
+                                             int k, NodeRegs* w) {
+#pragma unroll
+  for (int r = 0; r < kMaxR; ++r)
+    if (r < t.R) w->fr[r] = nr.fr[r] + vt.cum[(size_t)r * vt.rows + row];
+  if (vt.ports_after) {
+#pragma unroll
+    for (int p = 0; p < kMaxKP; ++p)
+      if (p < t.KP) w->pt[p] = vt.ports_after[(size_t)p * vt.rows + row];
+  }
+  w->slots_ok = count - k + 1 <= allowed;
+}
+// need of the pair on this lane's node: 0 fits as it stands, k >= 1 the shortest prefix, -1 never; *level = the reach level of a need
+// >= 1 (tier of victim need - 1, plus one), else 0. Called by EVERY lane of the wave (live == false: a lane past the table, which
+// touches no memory): the bisection runs while any lane still has an open interval, at most ceil(log2 len) steps of one gather and one
+// eval_pair. The node's registers are left as they were. Nothing is indexed by the tier or the step in registers.
+__device__ __forceinline__ int victim_need(const NodeTable& t, const SpecTable& s, const VictimTable& vt, int spec, int pin, int node,
+                                           bool live, const NodeRegs& nr, i64 count, i64 allowed, int limit, unsigned pre_mask,
+                                           unsigned filt_mask, int* level) {
+  int code = 0;
+  unsigned reason = 0;
+  *level = 0;
+  const bool fits = live && eval_pair(s, spec, pin, node, nr, pre_mask, filt_mask, &code, &reason);
+  int len = 0;
+  bool open = live && !fits && limit > 0 && reach_code_opens(code);
+  if (open) {
+    len = vt.tier_end[(size_t)(limit - 1) * t.n + node];
+    open = len > 0;
+  }
+  size_t base = 0;
+  NodeRegs w = nr;
+  if (open) {  // with ALL len victims gone: a lane that still fails is never
+    base = (size_t)vt.seg_base[node];
+    victim_state(t, vt, nr, base + (size_t)len - 1, count, allowed, len, &w);
+    open = eval_pair(s, spec, pin, node, w, pre_mask, filt_mask, &code, &reason);
+  }
+  int lo = 0, hi = open ? len : 0;  // on an open lane state(lo) fails and state(hi) fits; every other lane has no interval
+  while (__ballot(hi - lo > 1)) {
+    if (hi - lo > 1) {
+      const int mid = lo + (hi - lo) / 2;
+      victim_state(t, vt, nr, base + (size_t)mid - 1, count, allowed, mid, &w);
+      if (eval_pair(s, spec, pin, node, w, pre_mask, filt_mask, &code, &reason)) hi = mid;
+      else lo = mid;
+    }
+  }
+  if (!open) return fits ? 0 : -1;
+  int lv = 1;
+  for (int tier = 0; tier + 1 < limit; ++tier) lv += vt.tier_end[(size_t)tier * t.n + node] < hi ? 1 : 0;
+  *level = lv;
+  return hi;
+}
+
+// Grid of k_explain / k_preempt_reach: blockIdx.x = chunk of kExplainTasks tasks (spec, pin, limit), blockIdx.y = 256 nodes, lane =
+// node; the node columns are loaded once per chunk. Per task the three node counts are ballot popcounts, the sum of need a wave sum,
+// the best key (k_preempt_reach's packing, the exact need in the victim field) one wave MIN; the block's waves meet in LDS; then one
+// global integer add per non-zero cell of cells[tasks][16] and one 64-bit MIN per task into best[tasks]. Cell [3] is the `unsupported`
+// flag.
+__global__ __launch_bounds__(kBlock) void k_preempt_victims(NodeTable t, SpecTable s, VictimTable vt, int n_tasks,
+                                                            const int* __restrict__ task_spec, const int* __restrict__ task_pin,
+                                                            const int* __restrict__ task_limit, int node_offset, unsigned pre_mask,
+                                                            unsigned filt_mask, i64* __restrict__ cells, u64* __restrict__ best) {
+  __shared__ int acc[kExplainTasks * kVictimAcc];
+  __shared__ u64 accsum[kExplainTasks];
+  __shared__ u64 accbest[kExplainTasks];
+  for (int i = threadIdx.x; i < kExplainTasks * kVictimAcc; i += kBlock) acc[i] = 0;
+  if (threadIdx.x < kExplainTasks) accsum[threadIdx.x] = 0, accbest[threadIdx.x] = ~0ull;
+  __syncthreads();
+  const int lane = threadIdx.x % kWave;
+  bool live;
+  const int n = headroom_node(t, &live);
+  const int k0 = blockIdx.x * kExplainTasks, kend = min(k0 + kExplainTasks, n_tasks);
+  if (__ballot(live)) {  // (wave-uniform: a wave wholly past N skips the walk, not the barriers)
+    NodeRegs nr;
+    load_node(t, n, &nr);
+    const i64 count = live ? (i64)t.count[n] : 0, allowed = live ? (i64)t.allowed[n] : 0;
+    for (int k = k0; k < kend; ++k) {
+      int level = 0;
+      const int need = victim_need(t, s, vt, task_spec[k], task_pin[k], n, live, nr, count, allowed, task_limit[k], pre_mask, filt_mask, &level);
+      const u64 opened = __ballot(live && need >= 1);
+      const int c0 = __popcll(__ballot(live && need == 0)), c1 = __popcll(opened), c2 = __popcll(__ballot(live && need < 0));
+      const int mine = lane == 0 ? c0 : lane == 1 ? c1 : c2;
+      if (lane < 3 && mine) atomicAdd(&acc[(k - k0) * kVictimAcc + lane], mine);
+      if (opened) {
+        const bool has = live && need >= 1;
+        u64 key = ~0ull, sum = has ? (u64)need : 0;
+        if (has) key = ((u64)level << kReachLevelShift) | ((u64)min((i64)need, kReachPodsMax) << kReachPodsShift) | (u64)(unsigned)(node_offset + n);
+#pragma unroll
+        for (int off = kWave / 2; off > 0; off >>= 1) {
+          const u64 o = (u64)__shfl_xor((unsigned long long)key, off, kWave);
+          key = o < key ? o : key;
+          sum += (u64)__shfl_xor((unsigned long long)sum, off, kWave);
+        }
+        if (lane == 0) {
+          atomicMin((unsigned long long*)&accbest[k - k0], (unsigned long long)key);
+          atomicAdd((unsigned long long*)&accsum[k - k0], (unsigned long long)sum);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < (kend - k0) * kVictimAcc; i += kBlock) {
+    const int v = acc[i];
+    if (v) atomicAdd((u64*)&cells[(size_t)(k0 + i / kVictimAcc) * kVictimCells + i % kVictimAcc], (u64)v);
+  }
+  if ((int)threadIdx.x < kend - k0) {
+    const u64 v = accbest[threadIdx.x], sum = accsum[threadIdx.x];
+    if (v != ~0ull) atomicMin((unsigned long long*)&best[k0 + threadIdx.x], (unsigned long long)v);
+    if (sum) atomicAdd((u64*)&cells[(size_t)(k0 + threadIdx.x) * kVictimCells + 8], sum);
+  }
+  headroom_unsupported(s, k0, kend, [&](int k) { return task_spec[k]; }, cells + 3, kVictimCells);
+}
+
+// need of ONE ask on every node of the table (thread = node, as k_preempt_reach_pod)
+__global__ __launch_bounds__(kBlock) void k_preempt_victims_pod(NodeTable t, SpecTable s, VictimTable vt, int spec, int pin, int limit,
+                                                                unsigned pre_mask, unsigned filt_mask, int* __restrict__ out) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  const bool live = i < t.n;
+  const int n = live ? i : -1;
+  NodeRegs nr;
+  load_node(t, n, &nr);
+  int level = 0;
+  const int need = victim_need(t, s, vt, spec, pin, n, live, nr, live ? (i64)t.count[n] : 0, live ? (i64)t.allowed[n] : 0, limit, pre_mask,
+                               filt_mask, &level);
+  if (live) out[n] = need;
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -258,10 +258,27 @@ struct ykhost {
   bool rc_uploaded = false;           // the engine holds the reclaim table of the current node table and bounds
   std::vector<int> rc_dirty_nodes;    // nodes whose pod list changed since (one column each at the next reach call)
   int64_t rc_uploads = 0, rc_patches = 0;
+  // ---- preemption victims (ykhost_preempt_victims): the victim table as the mirror keeps it — derived at the first victims call,
+  // patched segment by segment after it — and whether the engine holds it
+  struct VictimMirror {
+    bool built = false;      // the planes describe the mirror, but for the segments of the `dirty` nodes
+    bool on_device = false;  // the engine holds them (but for the segments of `to_push`)
+    std::vector<int> dirty;  // nodes whose pod list changed since
+    std::vector<int> to_push;
+    size_t T = 0, R = 0, KP = 0, N = 0, P = 0;
+    std::vector<std::string> scalar_names;  // the dictionaries the planes were encoded with: a mirror-only handle re-encodes per call
+    std::vector<HostPort> port_dict;
+    std::vector<int32_t> base, cap, tier_end;  // [N], [N], [T][N]
+    std::vector<int64_t> cum;                  // [R][P]
+    std::vector<uint64_t> ports;               // [KP][P]
+    int64_t derived = 0, patches = 0;
+  } vt;
 
   void clear_state() {
     rc_uploaded = false;
     rc_dirty_nodes.clear();
+    vt.built = vt.on_device = false;
+    vt.dirty.clear();
     pool.clear();
     tpl_memo.clear();
     node_store.clear();
@@ -934,6 +951,8 @@ int full_sync(ykhost* h) {
   if (rc) return rc;
   h->rc_uploaded = false;  // (a new engine, or a node table of another size: the reclaim table goes with it)
   h->rc_dirty_nodes.clear();
+  h->vt.built = h->vt.on_device = false;  // (and the victim table; the dictionaries may have moved as well)
+  h->vt.dirty.clear();
   rc = ykpred_set_row_stride(h->eng, h->row_stride_words);
   if (rc) return fail(h, std::string("ykpred_set_row_stride: ") + ykpred_last_error(h->eng), rc);
   rc = ykpred_set_row_capacity(h->eng, 0);  // (re-applied below: a smaller table may follow a larger one)
@@ -1069,6 +1088,13 @@ int sync(ykhost* h) {
 // A node-level change that cannot introduce new dictionary entries (pod assumed / forgotten / removed).
 void touch_node(ykhost* h, int n) {
   if (h->rc_uploaded) h->rc_dirty_nodes.push_back(n);
+  if (h->vt.built) {
+    h->vt.dirty.push_back(n);
+    if (h->vt.dirty.size() > 4 * h->nodes.size() + 1024) {  // (nobody asked for long: deriving the table anew is the cheaper way back)
+      h->vt.built = h->vt.on_device = false;
+      h->vt.dirty.clear();
+    }
+  }
   if (!h->dirty_all) {
     h->dirty_nodes.push_back(n);
     h->eval_dirty_nodes.push_back(n);
@@ -3642,6 +3668,9 @@ int32_t ykhost_set_preemption_tiers(ykhost_t* h, const int32_t* bounds, int32_t 
   h->rc_bounds.assign(bounds, bounds + T);
   h->rc_uploaded = false;
   h->rc_dirty_nodes.clear();
+  h->vt.built = h->vt.on_device = false;
+  h->vt.dirty.clear();
+  if (T == 0 && h->eng) ykpred_set_victims(h->eng, nullptr);
   if (T == 0 && h->eng) ykpred_set_reclaim(h->eng, nullptr);
   return 0;
 }
@@ -3821,6 +3850,297 @@ int32_t ykhost_preempt_headroom_by_key(ykhost_t* h, const char* allocation_key, 
     return rc;
   }
   return ykhost_preempt_headroom(h, 1, &row, &want, out32);
+}
+
+// ---- preemption victims (ykpred_preempt_victims) --------------------------------------------------------------------------------------
+namespace {
+// order(n): the node's pods that are in a tier, by (priority, uid) ascending — tiers are monotone in the priority, so the pods of tiers
+// < L are a prefix for every L
+void victim_order(const ykhost* h, const NodeInfo& ni, std::vector<const Pod*>* order) {
+  order->clear();
+  for (const Pod* p : ni.pods)
+    if (reclaim_tier(h, p) >= 0) order->push_back(p);
+  std::sort(order->begin(), order->end(), [](const Pod* a, const Pod* b) { return a->priority != b->priority ? a->priority < b->priority : a->uid < b->uid; });
+}
+// One node's segment, a sibling of reclaim_column: tier_end[t * tstride], and per victim i of the order the PREFIX sum of the request
+// vectors at cum[r * pstride + i] and the node's port words once victims 0..i are gone at ports[k * pstride + i]. The ports follow
+// NodeInfo.RemovePod as append_victims does: a triple leaves the SET with its first holder.
+void victim_segment(const ykhost* h, const NodeInfo& ni, const std::vector<const Pod*>& order, size_t tstride, int32_t* tier_end, size_t pstride,
+                    int64_t* cum, uint64_t* ports) {
+  const int T = (int)h->rc_bounds.size(), R = h->enc.R, KP = h->enc.KP;
+  for (int t = 0; t < T; ++t) tier_end[(size_t)t * tstride] = 0;
+  std::vector<int64_t> sum((size_t)R, 0);
+  std::set<HostPort> used;
+  std::vector<uint64_t> bits((size_t)KP);
+  if (KP) used = ni.used_ports;
+  bool changed = true;
+  for (size_t i = 0; i < order.size(); ++i) {
+    const Pod* p = order[i];
+    for (int t = reclaim_tier(h, p); t < T; ++t) tier_end[(size_t)t * tstride] += 1;
+    const Resource& r = p->tpl->res;
+    sum[0] += r.milli_cpu;
+    sum[1] += r.memory;
+    sum[2] += r.ephemeral;
+    for (size_t s = 0; s < h->enc.scalar_names.size(); ++s) {
+      auto it = r.scalar.find(h->enc.scalar_names[s]);
+      if (it != r.scalar.end()) sum[3 + s] += it->second;
+    }
+    for (int k = 0; k < R; ++k) cum[(size_t)k * pstride + i] = sum[(size_t)k];
+    if (!KP) continue;
+    for (const HostPort& hp : template_host_ports(*p->tpl)) changed = used.erase(hp) > 0 || changed;
+    if (changed) h->enc.encode_used_ports(used, bits.data());
+    changed = false;
+    for (int k = 0; k < KP; ++k) ports[(size_t)k * pstride + i] = bits[(size_t)k];
+  }
+}
+bool same_ports(const std::vector<HostPort>& a, const std::vector<HostPort>& b) {
+  if (a.size() != b.size()) return false;
+  for (size_t i = 0; i < a.size(); ++i)
+    if (a[i] < b[i] || b[i] < a[i]) return false;
+  return true;
+}
+// The slack rule: a segment holds count + count / 2 + 4 rows, so a node takes half as many victims again (and four on an empty node)
+// before the whole table is derived anew.
+int32_t victim_capacity(size_t count) { return (int32_t)(count + count / 2 + 4); }
+
+// Brings the mirror's victim table up to date — the dictionaries are current: the caller has synced or encoded — and, with a device, the
+// engine's copy: the segments of the marked nodes are patched; the whole table is derived when there is none, the dimensions or the
+// dictionaries moved, or a segment outgrew its capacity.
+int victims_refresh(ykhost* h) {
+  ykhost::VictimMirror& v = h->vt;
+  const size_t T = h->rc_bounds.size(), R = (size_t)h->enc.R, KP = (size_t)h->enc.KP, N = h->nodes.size();
+  bool whole = !v.built || v.T != T || v.R != R || v.KP != KP || v.N != N;
+  if (!whole && h->device < 0) whole = v.scalar_names != h->enc.scalar_names || !same_ports(v.port_dict, h->enc.port_dict);
+  std::vector<const Pod*> order;
+  if (!whole) {
+    std::vector<int> todo;
+    todo.swap(v.dirty);
+    std::sort(todo.begin(), todo.end());
+    todo.erase(std::unique(todo.begin(), todo.end()), todo.end());
+    for (int n : todo) {
+      if (n < 0 || (size_t)n >= N) continue;
+      victim_order(h, *h->nodes[(size_t)n], &order);
+      if ((int64_t)order.size() > v.cap[(size_t)n]) {
+        whole = true;
+        break;
+      }
+      const size_t b = (size_t)v.base[(size_t)n];
+      victim_segment(h, *h->nodes[(size_t)n], order, N, v.tier_end.data() + n, v.P, v.cum.data() + b, KP ? v.ports.data() + b : nullptr);
+      v.to_push.push_back(n);
+      v.patches++;
+    }
+  }
+  if (whole) {
+    v.built = v.on_device = false;
+    v.dirty.clear();
+    v.to_push.clear();
+    v.T = T, v.R = R, v.KP = KP, v.N = N;
+    v.scalar_names = h->enc.scalar_names;
+    v.port_dict = h->enc.port_dict;
+    v.base.assign(N + 1, 0);
+    v.cap.assign(N + 1, 0);
+    std::vector<std::vector<const Pod*>> orders(N);
+    size_t P = 0;
+    for (size_t n = 0; n < N; ++n) {
+      victim_order(h, *h->nodes[n], &orders[n]);
+      v.base[n] = (int32_t)P;
+      v.cap[n] = victim_capacity(orders[n].size());
+      P += (size_t)v.cap[n];
+      if (P >= (1ull << 31)) return fail(h, "victim table: more than 2^31 - 1 rows", YKPRED_E_UNSUPPORTED);
+    }
+    v.P = P;
+    v.tier_end.assign(T * N + 1, 0);
+    v.cum.assign(R * P + 1, 0);
+    v.ports.assign(KP * P + 1, 0);
+    for (size_t n = 0; n < N; ++n)
+      victim_segment(h, *h->nodes[n], orders[n], N, v.tier_end.data() + n, P, v.cum.data() + (size_t)v.base[n], KP ? v.ports.data() + (size_t)v.base[n] : nullptr);
+    v.built = true;
+    v.derived++;
+  }
+  if (h->device < 0) {
+    v.to_push.clear();
+    return 0;
+  }
+  ykpred_victims_t vt{};
+  vt.tiers = (int32_t)T;
+  if (!v.on_device) {
+    vt.rows = (int64_t)v.P;
+    vt.seg_base = v.base.data();
+    vt.seg_cap = v.cap.data();
+    vt.tier_end = v.tier_end.data();
+    vt.cum = v.cum.data();
+    vt.ports_after = KP ? v.ports.data() : nullptr;
+    const int rc = ykpred_set_victims(h->eng, &vt);
+    if (rc) return fail(h, std::string("ykpred_set_victims: ") + ykpred_last_error(h->eng), rc);
+    v.on_device = true;
+    v.to_push.clear();
+    return 0;
+  }
+  std::vector<int> push;
+  push.swap(v.to_push);
+  std::vector<int32_t> te(T + 1);
+  std::vector<int64_t> cum;
+  std::vector<uint64_t> ports;
+  for (int n : push) {
+    const size_t b = (size_t)v.base[(size_t)n];
+    for (size_t t = 0; t < T; ++t) te[t] = v.tier_end[t * N + (size_t)n];
+    const size_t count = T ? (size_t)te[T - 1] : 0;
+    cum.assign(R * count + 1, 0);
+    ports.assign(KP * count + 1, 0);
+    for (size_t r = 0; r < R; ++r) std::copy_n(v.cum.data() + r * v.P + b, count, cum.data() + r * count);
+    for (size_t k = 0; k < KP; ++k) std::copy_n(v.ports.data() + k * v.P + b, count, ports.data() + k * count);
+    vt.rows = (int64_t)count;
+    vt.tier_end = te.data();
+    vt.cum = cum.data();
+    vt.ports_after = KP ? ports.data() : nullptr;
+    const int rc = ykpred_update_victims_node(h->eng, n, (int32_t)count, &vt);
+    if (rc) {
+      v.on_device = false;  // (the next call uploads the whole table)
+      return fail(h, std::string("ykpred_update_victims_node: ") + ykpred_last_error(h->eng), rc);
+    }
+  }
+  return 0;
+}
+// sync, the reclaim table (the engine wants it beside the victim table), then the victim table
+int victims_sync(ykhost* h, const char* name) {
+  int rc = reclaim_sync(h, name);
+  if (rc) return rc;
+  return victims_refresh(h);
+}
+// the uids of order(node) in tiers < limit, each followed by one NUL; → their number, written as far as whole uids fit
+int32_t victim_uids(const ykhost* h, int node, int limit, int64_t at_most, char* buf, int64_t len) {
+  std::vector<const Pod*> order;
+  victim_order(h, *h->nodes[(size_t)node], &order);
+  int32_t count = 0;
+  int64_t used = 0;
+  bool room = buf != nullptr;
+  for (const Pod* p : order) {
+    if (reclaim_tier(h, p) >= limit || count >= at_most) break;
+    count++;
+    if (room && used + (int64_t)p->uid.size() + 1 <= len) {
+      memcpy(buf + used, p->uid.c_str(), p->uid.size() + 1);
+      used += (int64_t)p->uid.size() + 1;
+    } else {
+      room = false;
+    }
+  }
+  return count;
+}
+}  // namespace
+
+int32_t ykhost_victim_stats(ykhost_t* h, int64_t* out2) {
+  YKHOST_LOCKED(h);
+  if (!out2) return fail(h, "victim_stats: bad argument", -1);
+  out2[0] = h->vt.derived;
+  out2[1] = h->vt.patches;
+  return 0;
+}
+
+int32_t ykhost_victim_table(ykhost_t* h, int32_t* dims, int32_t* seg_base, int32_t* seg_cap, int32_t* tier_end, int64_t* cum, uint64_t* ports_after) {
+  YKHOST_LOCKED(h);
+  if (!dims) return fail(h, "victim_table: bad argument", -1);
+  if (h->rc_bounds.empty()) return fail(h, "victim_table: no preemption tiers (ykhost_set_preemption_tiers)", YKPRED_E_STATE);
+  int rc = 0;
+  if (h->device < 0) {  // (a mirror-only handle encodes for the dictionaries alone, as ykhost_reclaim_table does)
+    EncodedTables T;
+    rc = encode_tables(h, &T);
+    h->dirty_all = true;
+    if (!rc) rc = victims_refresh(h);
+  } else {
+    rc = victims_sync(h, "victim_table");
+  }
+  if (rc) return rc;
+  const ykhost::VictimMirror& v = h->vt;
+  dims[0] = (int32_t)v.T, dims[1] = (int32_t)v.R, dims[2] = (int32_t)v.KP, dims[3] = (int32_t)v.N, dims[4] = (int32_t)v.P;
+  if (!seg_base || !seg_cap || !tier_end || !cum || !ports_after) return 0;
+  std::copy_n(v.base.begin(), v.N, seg_base);
+  std::copy_n(v.cap.begin(), v.N, seg_cap);
+  std::copy_n(v.tier_end.begin(), v.T * v.N, tier_end);
+  std::copy_n(v.cum.begin(), v.R * v.P, cum);
+  std::copy_n(v.ports.begin(), v.KP * v.P, ports_after);
+  return 0;
+}
+
+int32_t ykhost_victim_list(ykhost_t* h, int32_t node, int32_t limit, char* uids_buf, int64_t len, int32_t* count) {
+  YKHOST_LOCKED(h);
+  if (!count || len < 0) return fail(h, "victim_list: bad argument", -1);
+  *count = 0;
+  if (h->rc_bounds.empty()) return fail(h, "victim_list: no preemption tiers (ykhost_set_preemption_tiers)", YKPRED_E_STATE);
+  if (node < 0 || (size_t)node >= h->nodes.size()) return fail(h, "victim_list: node index out of range", YKPRED_E_INVALID);
+  if (limit < 0 || limit > (int)h->rc_bounds.size()) return fail(h, "victim_list: limit outside 0 .. tiers", YKPRED_E_INVALID);
+  *count = victim_uids(h, node, limit, INT64_MAX, uids_buf, len);
+  return 0;
+}
+
+int32_t ykhost_preempt_victims(ykhost_t* h, int32_t n, const int32_t* asks, int64_t* out_cells) {
+  YKHOST_LOCKED(h);
+  constexpr size_t B = YKPRED_VICTIM_CELLS;
+  if (n < 0 || (n > 0 && !out_cells)) return fail(h, "preempt_victims: bad argument", -1);
+  int rc = victims_sync(h, "preempt_victims");
+  if (rc) return rc;
+  int32_t world = 1;
+  ykpred_comm_info(h->eng, nullptr, &world, nullptr);
+  const int P = (int)h->pending.size();
+  for (int i = 0; i < n; ++i)
+    if ((asks ? asks[i] : i) < 0 || (asks ? asks[i] : i) >= P) return fail(h, "preempt_victims: ask index out of range", YKPRED_E_INVALID);
+  // (an ask routed to the CPU manager gets its status here; on a node-sharded handle every ask goes to the engine, as in ykhost_explain)
+  std::vector<int32_t> list, limits, slot;
+  for (int i = 0; i < n; ++i) {
+    const int row = asks ? asks[i] : i;
+    const Pod* p = h->pending[(size_t)row];
+    int64_t* c = out_cells + (size_t)i * B;
+    if (world <= 1 && h->enc.unsupported.count(p->tpl)) {
+      std::fill(c, c + B, (int64_t)0);
+      c[3] = 1;
+      c[4] = reclaim_limit(h, p);
+      c[6] = -1;
+    } else {
+      list.push_back(row);
+      limits.push_back(reclaim_limit(h, p));
+      slot.push_back(i);
+    }
+  }
+  if (list.empty() && world <= 1) return 0;
+  std::vector<int64_t> rows(list.size() * B);
+  rc = ykpred_preempt_victims(h->eng, (int32_t)list.size(), list.data(), limits.data(), h->alloc_pre, h->alloc_filt, rows.data());
+  if (rc) return fail(h, std::string("ykpred_preempt_victims: ") + ykpred_last_error(h->eng), rc);
+  for (size_t k = 0; k < list.size(); ++k) memcpy(out_cells + (size_t)slot[k] * B, rows.data() + k * B, B * sizeof(int64_t));
+  return 0;
+}
+
+int32_t ykhost_preempt_victims_nodes(ykhost_t* h, int32_t pod, int32_t* out) {
+  YKHOST_LOCKED(h);
+  if (!out) return fail(h, "preempt_victims_nodes: bad argument", -1);
+  int rc = victims_sync(h, "preempt_victims_nodes");
+  if (rc) return rc;
+  if (pod < 0 || pod >= (int)h->pending.size()) return fail(h, "preempt_victims_nodes: ask index out of range", YKPRED_E_INVALID);
+  rc = ykpred_preempt_victims_pod(h->eng, pod, reclaim_limit(h, h->pending[(size_t)pod]), h->alloc_pre, h->alloc_filt, out);
+  if (rc) return fail(h, std::string("ykpred_preempt_victims_pod: ") + ykpred_last_error(h->eng), rc);
+  return 0;
+}
+
+// One ask named as the core names it, one crossing: the cells, the best node by name and the uids of its victim prefix — in front of
+// the core's per-node predicate checks of a preemption attempt.
+int32_t ykhost_preempt_victims_by_key(ykhost_t* h, const char* allocation_key, int64_t* out16, char* best_node_name, int64_t name_len,
+                                      char* victim_uids_buf, int64_t uids_len) {
+  YKHOST_LOCKED(h);
+  if (!out16) return fail(h, "preempt_victims_by_key: bad argument", -1);
+  std::fill(out16, out16 + YKPRED_VICTIM_CELLS, (int64_t)0);
+  out16[6] = -1;
+  copy_out("", best_node_name, name_len);
+  if (victim_uids_buf && uids_len > 0) victim_uids_buf[0] = 0;
+  int32_t row = -1;
+  int rc = ask_row_by_key(h, allocation_key, &out16[3], &row);
+  if (rc) return rc;
+  rc = ykhost_preempt_victims(h, 1, &row, out16);
+  if (rc) return rc;
+  int32_t offset = 0;
+  ykpred_comm_info(h->eng, nullptr, nullptr, &offset);
+  const int64_t local = out16[6] - offset;
+  if (out16[6] < 0 || local < 0 || local >= (int64_t)h->nodes.size()) return 0;
+  copy_out(h->nodes[(size_t)local]->node.name, best_node_name, name_len);
+  if (victim_uids_buf && uids_len > 0) victim_uids(h, (int)local, (int)out16[4], out16[7], victim_uids_buf, uids_len);
+  return 0;
 }
 
 // ---- headroom per topology domain (ykpred_headroom_groups) --------------------------------------------------------------------------

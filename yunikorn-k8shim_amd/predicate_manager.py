@@ -63,6 +63,11 @@ REACH_NEVER, REACH_STATUS, REACH_LIMIT, REACH_BEST_LEVEL, REACH_BEST_NODE, REACH
 PREEMPT_HEADROOM_CELLS = 32
 PREEMPT_HEADROOM_COPIES, PREEMPT_HEADROOM_NODES, PREEMPT_HEADROOM_VICTIMS = 0, 9, 18
 PREEMPT_HEADROOM_STATUS, PREEMPT_HEADROOM_LIMIT, PREEMPT_HEADROOM_WANT, PREEMPT_HEADROOM_LEVEL = 27, 28, 29, 30
+# ykpred_preempt_victims: per ask int64[VICTIM_CELLS] = nodes with need 0, need >= 1, need -1, status (0 computed, 1 routed), the ask's
+# limit, the best node's level (0: none), the best node (lowest level, fewest victims, lowest index; -1: none), its need, the sum of need
+# over the nodes of [1], 0 ...
+VICTIM_CELLS = 16
+VICTIM_FIT, VICTIM_OPEN, VICTIM_NEVER, VICTIM_STATUS, VICTIM_LIMIT, VICTIM_BEST_LEVEL, VICTIM_BEST_NODE, VICTIM_BEST_NEED, VICTIM_TOTAL = range(9)
 
 
 def plugin_mask(names):
@@ -851,6 +856,88 @@ class GpuPredicateManager:
             raise KeyError(uid)
         self._check(rc)
         return out
+
+    # ---- preemption victims: the shortest victim prefix on every node ---------------------------------------------------
+    def preempt_victims(self, pods=None, pre_mask=None, filt_mask=None):
+        """Per ask the nodes by NEED, reduced on the device (ykpred_preempt_victims): np.int64[n, VICTIM_CELLS] — [VICTIM_FIT] nodes
+        the ask fits as they stand, [VICTIM_OPEN] nodes it fits once the first need >= 1 pods of order(n) are gone, [VICTIM_NEVER]
+        nodes no prefix opens, [VICTIM_STATUS] 1 for a routed ask, [VICTIM_LIMIT], [VICTIM_BEST_LEVEL], [VICTIM_BEST_NODE] (global
+        index, -1: none), [VICTIM_BEST_NEED], [VICTIM_TOTAL] the sum of need over the open nodes. pods: ask indices or UIDs in any
+        order, repeats allowed; None = every ask. Always the allocation-phase lists; explicit masks go to the engine with the limits
+        the host derives. Needs no evaluation and disturbs none."""
+        if pods is None:
+            count, ptr = self.num_pods, None
+        else:
+            idx = [p if isinstance(p, (int, np.integer)) else self.pod_index(p) for p in pods]
+            arr = np.ascontiguousarray(idx, dtype=np.int32)
+            count, ptr = len(arr), arr.ctypes.data
+        out = np.zeros((max(count, 1), VICTIM_CELLS), dtype=np.int64)
+        if pre_mask is None and filt_mask is None:
+            self._check(self._L.ykhost_preempt_victims(self._h, count, ptr, out.ctypes.data))
+        else:
+            pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
+            self.victim_table(planes=False)   # (syncs the tables, the reclaim and the victim table)
+            limits = np.zeros(max(count, 1), dtype=np.int32)
+            self._check(self._L.ykhost_preempt_limits(self._h, count, ptr, limits.ctypes.data))
+            if ptr is None:
+                arr = np.arange(count, dtype=np.int32)
+                ptr = arr.ctypes.data
+            self._pcheck(self._P.ykpred_preempt_victims(self.engine, count, ptr, limits.ctypes.data, pre, filt, out.ctypes.data))
+        return out[:count].copy()
+
+    def preempt_victims_nodes(self, pod):
+        """need of ONE ask (index or UID) on every node (ykpred_preempt_victims_pod): np.int32[N] — 0 fits as it stands, k >= 1 the
+        first k pods of victim_list(node) must go, -1 never. On a node-sharded manager: this shard's nodes."""
+        p = pod if isinstance(pod, (int, np.integer)) else self.pod_index(pod)
+        out = np.zeros(max(self.num_nodes, 1), dtype=np.int32)
+        self._check(self._L.ykhost_preempt_victims_nodes(self._h, int(p), out.ctypes.data))
+        return out[:self.num_nodes].copy()
+
+    def victim_list(self, node, limit):
+        """The uids of order(node) — the node's pods in a tier, by (priority, uid) ascending — in tiers < limit
+        (ykhost_victim_list; works without a device): the first `need` of them are the victims."""
+        n = node if isinstance(node, (int, np.integer)) else self.node_index(node)
+        count = C.c_int32(0)
+        size = 1 << 12
+        while True:
+            buf = C.create_string_buffer(size)
+            self._check(self._L.ykhost_victim_list(self._h, int(n), int(limit), C.addressof(buf), size, C.addressof(count)))
+            uids = [u.decode() for u in buf.raw.split(b"\0")[:count.value]]
+            if all(uids) or size > (1 << 28):
+                return uids
+            size *= 8
+
+    def preempt_victims_by_key(self, uid):
+        """One ask by allocation key in one crossing (ykhost_preempt_victims_by_key) → (np.int64[VICTIM_CELLS], best node name or "",
+        the uids of its victim prefix). Raises UnsupportedAsk for a routed ask, KeyError for an unknown pod."""
+        out = np.zeros(VICTIM_CELLS, dtype=np.int64)
+        name = C.create_string_buffer(512)
+        uids = C.create_string_buffer(1 << 16)
+        rc = self._L.ykhost_preempt_victims_by_key(self._h, uid.encode(), out.ctypes.data, name, 512, C.addressof(uids), 1 << 16)
+        if rc == -13:
+            raise UnsupportedAsk(self._L.ykhost_last_error(self._h).decode())
+        if rc in (-10, -12):
+            raise KeyError(uid)
+        self._check(rc)
+        victims = [u.decode() for u in uids.raw.split(b"\0")[:int(out[VICTIM_BEST_NEED])] if u] if name.value else []
+        return out, name.value.decode(), victims
+
+    def victim_table(self, planes=True):
+        """The victim table as the mirror keeps it — patched segment by segment, not derived afresh (ykhost_victim_table; works
+        without a device) → dict(seg_base np.int32[N], seg_cap np.int32[N], tier_end np.int32[T, N], cum np.int64[R, P], ports_after
+        np.uint64[KP, P], derived, patches)."""
+        dims = np.zeros(5, dtype=np.int32)
+        self._check(self._L.ykhost_victim_table(self._h, dims.ctypes.data, None, None, None, None, None))
+        if not planes:
+            return None
+        T, R, KP, N, P = (int(x) for x in dims)
+        arrays = [np.zeros(N, dtype=np.int32), np.zeros(N, dtype=np.int32), np.zeros((T, N), dtype=np.int32), np.zeros((R, P), dtype=np.int64),
+                  np.zeros((KP, P), dtype=np.uint64)]
+        pad = [np.zeros(1, dtype=a.dtype) if a.size == 0 else a for a in arrays]
+        self._check(self._L.ykhost_victim_table(self._h, dims.ctypes.data, *(a.ctypes.data for a in pad)))
+        stats = np.zeros(2, dtype=np.int64)
+        self._check(self._L.ykhost_victim_stats(self._h, stats.ctypes.data))
+        return dict(zip(("seg_base", "seg_cap", "tier_end", "cum", "ports_after"), arrays), derived=int(stats[0]), patches=int(stats[1]))
 
     def reclaim_table(self):
         """The reclaim planes the mirror derives from the pods on its nodes (ykhost_reclaim_table; works without a device) →
