@@ -404,6 +404,34 @@ int32_t ykhost_victim_table(ykhost_t* h, int32_t* dims /* [5] */, int32_t* seg_b
                             uint64_t* ports_after);
 int32_t ykhost_victim_stats(ykhost_t* h, int64_t* out2 /* [2] */);
 
+/* PREEMPTION ROUND (ykpred.h: ykpred_preempt_round) — conflict-resolved victim plans for a list of asks: what the caller's loop of
+ * ykhost_preempt_victims_by_key, ykhost_remove_pod per victim and ykhost_assume_pod per ask answers, in one call that changes nothing
+ * in the mirror or on the device. The asks are processed in list order, each under the state the earlier ones left behind; a repeated
+ * ask is one more copy (a gang). Limits are the mirror's (ykhost_set_preemption_tiers); always the ALLOCATION-phase plugin lists.
+ *   ykhost_preempt_round          syncs, brings the reclaim and the victim table up to date as ykhost_preempt_victims does and makes ONE
+ *                                 engine call: out_cells[i] = the YKPRED_PREEMPT_ROUND_CELLS cells of ask i of the list (NULL = asks
+ *                                 0..n-1), out_summary = the 8 summary cells. An ask routed to the CPU manager gets outcome 3 without
+ *                                 taking a turn. Collective on a node-sharded handle: every rank passes the same asks.
+ *   ykhost_preempt_round_by_keys  ONE crossing: allocation keys (pod UIDs) in; beside the cells, node_names receives per ask the node
+ *                                 by NAME ("" at outcome 2..4, or when the node lies on another shard), each followed by one NUL, and
+ *                                 victim_uids the uids of order(node)[from .. from + extra) of every ask in list order, each followed by
+ *                                 one NUL (ask i owns the next cells[i][3] of them). needed2 = { bytes of names, bytes of uids } the
+ *                                 answer needs; a buffer too short holds what fits whole. YKHOST_E_POD_NOT_FOUND / YKHOST_E_NOT_AN_ASK
+ *                                 for a key that names no ask (nothing is computed).
+ *   ykhost_preempt_gang_by_key    the same over `want` copies of one ask: where the gang goes and at whose cost (ykhost_preempt_headroom
+ *                                 says only whether it fits at a level).
+ *   ykhost_victim_range           the uids of order(node)[from .. from + count), NUL-separated, *got of them, *needed bytes: the slice
+ *                                 the by-keys call hands out. Works on a mirror-only handle. */
+int32_t ykhost_preempt_round(ykhost_t* h, int32_t n, const int32_t* asks /* NULL = asks 0..n-1 */, int64_t* out_cells /* [n][8] */,
+                             int64_t* out_summary /* [8] */);
+int32_t ykhost_preempt_round_by_keys(ykhost_t* h, int32_t n, const char* const* allocation_keys, int64_t* out_cells /* [n][8] */,
+                                     int64_t* out_summary /* [8] */, char* node_names, int64_t names_len, char* victim_uids, int64_t uids_len,
+                                     int64_t* needed2 /* [2] or NULL */);
+int32_t ykhost_preempt_gang_by_key(ykhost_t* h, const char* allocation_key, int32_t want, int64_t* out_cells /* [want][8] */,
+                                   int64_t* out_summary /* [8] */, char* node_names, int64_t names_len, char* victim_uids, int64_t uids_len,
+                                   int64_t* needed2 /* [2] or NULL */);
+int32_t ykhost_victim_range(ykhost_t* h, int32_t node, int32_t from, int32_t count, char* uids_buf, int64_t len, int32_t* got, int64_t* needed);
+
 /* Engine calls that came back YKPRED_E_DEVICE / YKPRED_E_NOMEM so far (failed allocation, lost device). Each one marks the whole
  * device state stale: the failing call returns its error (Predicates() < 0: the Go manager routes the ask to the CPU predicate
  * manager — SURVEY.md §5, "must degrade, never fail scheduling"), the mirror stays intact, and the next ykhost_sync /

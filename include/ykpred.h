@@ -38,7 +38,8 @@
 extern "C" {
 #endif
 
-/* (ykpred_preempt_victims + ykpred_preempt_victims_pod + ykpred_set_victims + ykpred_update_victims_node + YKPRED_VICTIM_CELLS arrived
+/* (ykpred_preempt_round + YKPRED_PREEMPT_ROUND_CELLS arrived WITHIN version 4 too: dlsym("ykpred_preempt_round"))
+ * (ykpred_preempt_victims + ykpred_preempt_victims_pod + ykpred_set_victims + ykpred_update_victims_node + YKPRED_VICTIM_CELLS arrived
  *    WITHIN version 4 too: dlsym("ykpred_preempt_victims"))
  * (ykpred_preempt_headroom + ykpred_preempt_headroom_pod + YKPRED_PREEMPT_HEADROOM_CELLS arrived WITHIN version 4 too:
  *    dlsym("ykpred_preempt_headroom"))
@@ -831,6 +832,56 @@ int32_t ykpred_preempt_victims(ykpred_engine_t* e, int32_t n_asks, const int32_t
  * on a sharded engine. */
 int32_t ykpred_preempt_victims_pod(ykpred_engine_t* e, int32_t pod_index, int32_t limit, uint32_t prefilter_plugins, uint32_t filter_plugins,
                                    int32_t* out /* [N] */);
+
+/* PREEMPTION ROUND — conflict-resolved victim plans for a LIST of asks: the counterpart of ykpred_allocate_round for
+ * preemption. The asks are processed IN LIST ORDER, each under the state the earlier asks of the list left behind, in one call with no
+ * host step in between. A gang's plan is the call with the ask repeated: repeats are NOT deduplicated, each occurrence is one more
+ * copy; limits may come in any order.
+ *
+ * ROUND STATE, per node n, zero at the start of EVERY call; nothing persists, no table is changed, no evaluation is invalidated:
+ *   taken[n]          the prefix of order(n) already claimed
+ *   placed_req[r][n]  the summed request vectors of the asks the round placed on n
+ *   placed_pods[n]    their number
+ *   placed_ports[p][n] the OR of their wanted dictionary port words
+ * state(n, k), k >= taken[n] = the node as ykpred_preempt_victims sees it with victims 0..k-1 gone, and the round's pods on it: free
+ *   values free + cum[k-1] - placed_req (no cum term at k == 0), the slot test on count - k + placed_pods, port words
+ *   (k >= 1 ? ports_after[k-1] : ports) | placed_ports; the topology PreFilter state is frozen, as everywhere in §4.16-4.18.
+ * need'(a, n), at the ask's turn: the smallest k in [taken[n], hi] whose state passes Predicates, hi = max(taken[n],
+ *   tier_end[limit-1][n]) (hi = taken[n] at limit 0), reported as extra = k - taken[n]; -1 when no k of the interval passes or the
+ *   failure at k == taken[n] is one no removal changes. Monotone in k by §4.18's argument (the overlay is constant in k): a bisection.
+ * CHOICE: among the nodes with need' >= 0 the minimum of ykpred_preempt_reach's packed key level | extra | global node — level 0 for
+ *   extra == 0, else tier(order(n)[k-1]) + 1; extra saturates at 2^28 - 1 (a table with a longer segment: YKPRED_E_UNSUPPORTED). So an
+ *   ask that fits somewhere with no further victim — a node an earlier ask of the round opened counts — goes to the lowest-index such
+ *   node; every other ask to the lowest level, then the fewest further victims, then the lowest index.
+ * APPLY, on the chosen node: taken += extra, placed_req += req(a), placed_pods += 1, placed_ports |= wanted(a). Asks placed by the
+ *   round are never victims of later asks; a skipped ask (outcome 2, 3, 4) changes nothing. */
+#define YKPRED_PREEMPT_ROUND_CELLS 8
+/* per ask, in list order, int64[8]:
+ *  [0]  outcome: 0 placed with no further victim; 1 placed by preemption; 2 nowhere; 3 the spec is YKPRED_SPEC_UNSUPPORTED;
+ *       4 COUPLED by exactly ykpred_headroom's rule (the ask's verdicts read the topology histograms under these lists)
+ *  [1]  the node, a GLOBAL index on a sharded engine, or -1
+ *  [2]  from = taken[node] before the ask: its victims are order(node)[from .. from + extra - 1]
+ *  [3]  extra
+ *  [4]  the level
+ *  [5]  the limit, echoed
+ *  [6]  nodes with need' >= 0 at the ask's turn
+ *  [7]  the sum of extra over the nodes with extra >= 1 at its turn
+ * ([6] and [7]: a wrong overlay on a node that was NOT chosen still changes an output.) At outcome 2..4: [1] == -1, [2..4] == 0, and
+ * [6], [7] == 0.
+ * out_summary, int64[8]: [0..4] asks per outcome, [5] victims in all (the sum of [3]), [6] distinct nodes touched, [7] 0.
+ * IDENTITIES: (1) with non-increasing limits and no coupled ask the round equals, step by step, the host loop "need per node via
+ *   ykpred_preempt_victims_pod → the victims removed from the node → the ask assumed on it" on fresh tables; (2) a round of W repeats of
+ *   a status-0 ask places exactly min(W, ykpred_preempt_headroom copies(limit)) of them; (3) a round of ONE ask has [4], [1], [3] ==
+ *   ykpred_preempt_victims cells [5], [6], [7] when cell [0] there is 0 (and [1] == the first fitting node otherwise).
+ * Errors as ykpred_preempt_victims; n_asks == 0 is YKPRED_OK (the summary is zeroed); a table of N == 0 nodes gives outcome 2 for
+ *   every evaluated ask. Reads the TABLES only; prepares the topology histograms as ykpred_query does; ONE query; roctx range
+ *   "ykpred:preempt_round". All launches are plain launches queued on the engine's stream, with one readback at the end.
+ * NODE-SHARDED engines: COLLECTIVE — the agreement all-gather first (it covers the list and the limits); per evaluated ask one
+ *   all-reduce MIN of the packed key and one all-reduce SUM of the two counts, on the stream; every rank then applies the same decision,
+ *   the owning shard moves its state; one all-reduce MAX of the cells at the end ([2] is the owner's). All ranks return the same cells. */
+int32_t ykpred_preempt_round(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks /* host, ask indices, list order, repeats = copies */,
+                             const int32_t* limits /* host, [n_asks], 0..T */, uint32_t prefilter_plugins, uint32_t filter_plugins,
+                             int64_t* out_cells /* host, [n_asks][YKPRED_PREEMPT_ROUND_CELLS] */, int64_t* out_summary /* host, [8] */);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Multi-GPU: node-axis shards. One engine per GPU / process holds a contiguous shard of the node table and

@@ -728,6 +728,89 @@ func (m *gpuPredicateManager) PreemptionVictims(pod *v1.Pod) (fits, reachable, n
 	}
 }
 
+// PreemptionPlan is one ask's turn in a PreemptionRound: Outcome 0 placed with no further victim, 1 placed by preemption, 2 nowhere, 3 routed to
+// the CPU predicate manager, 4 coupled through a topology constraint (not planned here); Victims are the pods to evict on Node, in order.
+type PreemptionPlan struct {
+	Outcome int
+	Node    string
+	Level   int
+	Victims []string
+}
+
+// PreemptionRound plans the preemptions of a LIST of asks in one crossing (ykhost_preempt_round_by_keys): the asks take their turn in
+// list order, each under the state the earlier ones left behind — victims already claimed stay claimed, a placed ask holds its share
+// of the node — so two asks are never handed the same victims and the copies of a gang (the ask repeated) spread as they really
+// would. Nothing in the cache or on the device changes. The call site is where the core works through the starved asks of a queue in
+// one scheduling cycle: it replaces the per-ask loop PreemptionVictims → RemovePod per victim → AssumePod. ok == false when a pod is not
+// a mirrored ask, no tiers are set or the engine failed: the caller plans ask by ask as before.
+func (m *gpuPredicateManager) PreemptionRound(pods []*v1.Pod) (plans []PreemptionPlan, victimsInAll int64, ok bool) {
+	n := len(pods)
+	if n == 0 {
+		return nil, 0, true
+	}
+	keys := make([]*C.char, n)
+	for i, pod := range pods {
+		if pod == nil {
+			for _, k := range keys[:i] {
+				C.free(unsafe.Pointer(k))
+			}
+			return nil, 0, false
+		}
+		keys[i] = C.CString(string(pod.UID))
+	}
+	defer func() {
+		for _, k := range keys {
+			C.free(unsafe.Pointer(k))
+		}
+	}()
+	cells := make([]C.int64_t, 8*n)
+	var summary [8]C.int64_t
+	var needed [2]C.int64_t
+	namesLen, uidsLen := C.int64_t(256*n), C.int64_t(1<<16)
+	for {
+		names := (*C.char)(C.malloc(C.size_t(namesLen)))
+		uids := (*C.char)(C.malloc(C.size_t(uidsLen)))
+		rc := C.ykhost_preempt_round_by_keys(m.host, C.int32_t(n), (**C.char)(unsafe.Pointer(&keys[0])), &cells[0], &summary[0], names, namesLen,
+			uids, uidsLen, &needed[0])
+		if rc == 0 && (needed[0] > namesLen || needed[1] > uidsLen) { // (the round starts from zero state: asking again is exact)
+			C.free(unsafe.Pointer(names))
+			C.free(unsafe.Pointer(uids))
+			namesLen, uidsLen = needed[0]+1, needed[1]+1
+			continue
+		}
+		if rc == 0 {
+			plans = make([]PreemptionPlan, n)
+			name, uid := names, uids
+			for i := range plans {
+				c := cells[8*i : 8*i+8]
+				plans[i] = PreemptionPlan{Outcome: int(c[0]), Node: C.GoString(name), Level: int(c[4])}
+				name = (*C.char)(unsafe.Add(unsafe.Pointer(name), len(plans[i].Node)+1))
+				if plans[i].Node == "" {
+					continue
+				}
+				for k := int64(0); k < int64(c[3]); k++ {
+					v := C.GoString(uid)
+					plans[i].Victims = append(plans[i].Victims, v)
+					uid = (*C.char)(unsafe.Add(unsafe.Pointer(uid), len(v)+1))
+				}
+			}
+		}
+		C.free(unsafe.Pointer(names))
+		C.free(unsafe.Pointer(uids))
+		switch {
+		case rc == 0:
+			return plans, int64(summary[5]), true
+		case rc == C.YKHOST_E_POD_NOT_FOUND || rc == C.YKHOST_E_NOT_AN_ASK:
+			m.Counters.RoutedNotMirrored.Add(1)
+		default:
+			m.Counters.RoutedOnError.Add(1)
+			log.Log(log.ShimPredicates).Warn("GPU predicate engine error, no preemption round",
+				zap.String("error", C.GoString(C.ykhost_last_error(m.host))))
+		}
+		return nil, 0, false
+	}
+}
+
 // ResidentStats: Predicates() calls answered from the mirrored resident answer, per pair because the node's column changed,
 // by whole-ask device queries, and the answer / failing-plugin fetches behind them.
 func (m *gpuPredicateManager) ResidentStats() (resident, dirtyColumn, query, answerFetches, codeFetches int64) {

@@ -14,6 +14,8 @@ from .predicate_manager import (ALL_PLUGINS, EXPLAIN_BINS, EXPLAIN_FIT, EXPLAIN_
                                 PREEMPT_HEADROOM_STATUS, PREEMPT_HEADROOM_VICTIMS, PREEMPT_HEADROOM_WANT,
                                 VICTIM_BEST_LEVEL, VICTIM_BEST_NEED, VICTIM_BEST_NODE, VICTIM_CELLS, VICTIM_FIT, VICTIM_LIMIT, VICTIM_NEVER, VICTIM_OPEN,
                                 VICTIM_STATUS, VICTIM_TOTAL,
+                                PREEMPT_ROUND_CELLS, PREEMPT_ROUND_EXTRA, PREEMPT_ROUND_FROM, PREEMPT_ROUND_LEVEL, PREEMPT_ROUND_LIMIT,
+                                PREEMPT_ROUND_NODE, PREEMPT_ROUND_OPEN, PREEMPT_ROUND_OUTCOME, PREEMPT_ROUND_TOTAL,
                                 GpuPredicateManager,
                                 PredicateError, UnsupportedAsk, plugin_mask)
 

@@ -162,6 +162,7 @@ def load_ykpred():
     L.ykpred_update_victims_node.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(YkpredVictims)]
     L.ykpred_preempt_victims.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     L.ykpred_preempt_victims_pod.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.ykpred_preempt_round.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     L.ykpred_preempt_headroom.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     L.ykpred_preempt_headroom_pod.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
     _pred = L
@@ -263,6 +264,12 @@ def load_ykhost():
     L.ykhost_preempt_victims_by_key.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_int64]
     L.ykhost_victim_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ykhost_victim_stats.argtypes = [C.c_void_p, C.c_void_p]
+    L.ykhost_preempt_round.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ykhost_preempt_round_by_keys.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                               C.c_void_p]
+    L.ykhost_preempt_gang_by_key.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                             C.c_void_p]
+    L.ykhost_victim_range.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.ykhost_preempt_headroom.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ykhost_preempt_headroom_nodes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.ykhost_preempt_headroom_by_key.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p]

@@ -292,6 +292,8 @@ struct ykpred_engine {
   int vt_tiers = 0;                                       // 0 = no table
   size_t vt_rows = 0;
   bool vt_ports = false;
+  int64_t vt_max_cap = 0;  // the longest segment's capacity (ykpred_preempt_round packs a prefix length into 28 bits)
+  DevBuf d_pround;         // ykpred_preempt_round: [asks][8] cells | [asks] best keys | [asks][2] counts | the round's state columns
   DevBuf d_bytes_gather;  // ykpred_comm_allgather_bytes
   DevBuf d_topo_agree;  // node-sharded: the shape of every rank's topology histograms (agree_topology)
   u64 dict_digest = 0;  // ykpred_set_dictionary_digest
@@ -1790,7 +1792,7 @@ void ykpred_destroy(ykpred_engine_t* e) {
                     &e->d_class_sig_ident, &e->d_expand_count, &e->d_layout_hash, &e->d_gathered_pod_class, &e->d_row_pod,
                     &e->d_round, &e->d_fx_off, &e->d_fx_cls, &e->d_fx_cnt, &e->d_fx_occ, &e->d_sp_sig_of, &e->d_class_list_b, &e->d_gathered, &e->d_gathered_map,
                     &e->d_xkey, &e->d_xcand, &e->d_reach, &e->d_rc_req, &e->d_rc_pods, &e->d_rc_ports, &e->d_victims,
-                    &e->d_vt_base, &e->d_vt_tier_end, &e->d_vt_cum, &e->d_vt_ports})
+                    &e->d_vt_base, &e->d_vt_tier_end, &e->d_vt_cum, &e->d_vt_ports, &e->d_pround})
     b->release();
   if (e->ev_ready)
     for (auto& ev : e->ev) (void)hipEventDestroy(ev);
@@ -5070,6 +5072,8 @@ int32_t ykpred_set_victims(ykpred_engine_t* e, const ykpred_victims_t* vt) {
   e->h_vt_cap.assign(vt->seg_cap, vt->seg_cap + N);
   e->vt_rows = P;
   e->vt_ports = ports;
+  e->vt_max_cap = 0;
+  for (size_t n = 0; n < N; ++n) e->vt_max_cap = std::max<int64_t>(e->vt_max_cap, vt->seg_cap[n]);
   e->vt_tiers = vt->tiers;
   return YKPRED_OK;
 }
@@ -5213,6 +5217,91 @@ int32_t ykpred_preempt_victims_pod(ykpred_engine_t* e, int32_t pod, int32_t limi
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, e->d_scratch.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
+  return YKPRED_OK;
+}
+
+// Victim plans for a list of asks, conflict-resolved: per ask one k_preempt_round_step over every node and one
+// k_preempt_round_apply wave, queued back to back on the engine's stream with the round's zeroed state columns between them; one
+// readback at the end. headroom_prepare does the checks and the agreement; its tasks are not used (every occurrence is its own turn).
+int32_t ykpred_preempt_round(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, const int32_t* limits, uint32_t pre, uint32_t filt,
+                             int64_t* out_cells, int64_t* out_summary) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:preempt_round");
+  if (e) e->n_queries++;
+  static_assert(ykk::kPreemptRoundCells == YKPRED_PREEMPT_ROUND_CELLS, "k_preempt_round_apply writes the layout of ykpred.h");
+  constexpr size_t B = YKPRED_PREEMPT_ROUND_CELLS;
+  if (!e) return YKPRED_E_INVALID;
+  const bool args_ok = out_summary && (n_asks <= 0 || (asks && limits && out_cells));
+  auto more_checks = [&](std::string* why) -> int {
+    if (e->vt_tiers == 0 || e->vt_tiers != e->rc_tiers) return *why = "preempt_round: no victim table (ykpred_set_victims)", YKPRED_E_STATE;
+    if (e->vt_max_cap > ykk::kReachPodsMax) return *why = "preempt_round: a segment of more than 2^28 - 1 rows", YKPRED_E_UNSUPPORTED;
+    for (int i = 0; i < n_asks; ++i)
+      if (limits[i] < 0 || limits[i] > e->vt_tiers) return *why = "preempt_round: limit outside 0 .. tiers", YKPRED_E_INVALID;
+    return YKPRED_OK;
+  };
+  // (the plugin lists too: which asks are settled as coupled — and so which all-reduces are issued — depends on them)
+  u64 more = tune_hash({(u64)(uint32_t)e->vt_tiers, 0x726f756eull, (u64)pre, (u64)filt});
+  if (n_asks > 0 && args_ok)
+    for (int i = 0; i < n_asks; ++i) more = tune_hash({(u64)(uint32_t)limits[i]}, more);
+  HeadroomTasks tasks;
+  tasks.need_fit = false;
+  tasks.other_causes = "bad argument, no victim table, a limit outside 0 .. tiers, tables not uploaded, an index out of range or stale topology histograms";
+  bool run = false;
+  const int32_t rc = headroom_prepare(e, "preempt_round", n_asks, asks, args_ok, pre, filt, more_checks, more, &tasks, &run);
+  if (out_summary && (run || rc == YKPRED_OK)) std::fill(out_summary, out_summary + B, (int64_t)0);
+  if (!run) return rc;
+  const bool sharded = e->comm && e->comm_world > 1;
+  hipStream_t st = e->own_stream;
+  const size_t A = (size_t)n_asks, N = (size_t)e->N, R = (size_t)e->R, KP = (size_t)e->KP;
+  // one buffer: cells [A][8] | best keys [A] | counts [A][2] | placed_req [R][N] | placed_ports [KP][N] | taken [N] | placed_pods [N]
+  const size_t state_bytes = (R + KP) * N * sizeof(int64_t) + 2 * N * sizeof(int32_t);
+  HIPCHK(e->d_pround.ensure(A * (B + 3) * sizeof(int64_t) + state_bytes + 64));
+  int64_t* d_cells = e->d_pround.as<int64_t>();
+  int64_t* d_best = d_cells + A * B;
+  int64_t* d_counts = d_best + A;
+  ykk::PreemptRoundState rs;
+  rs.placed_req = (ykk::i64*)(d_counts + 2 * A);
+  rs.placed_ports = (ykk::u64*)(rs.placed_req + R * N);
+  rs.taken = (int*)(rs.placed_ports + KP * N);
+  rs.placed_pods = rs.taken + N;
+  HIPCHK(hipMemsetAsync(d_best, 0x7f, A * sizeof(int64_t), st));  // (level field 15: no node)
+  HIPCHK(hipMemsetAsync(d_counts, 0, 2 * A * sizeof(int64_t) + state_bytes, st));
+  const ykk::NodeTable nt = node_table(e);
+  const ykk::SpecTable stab = spec_table(e);
+  const ykk::VictimTable vt = victim_table(e);
+  const int offset = sharded ? e->node_offset : 0;
+  const dim3 grid((unsigned)((N + ykk::kBlock - 1) / ykk::kBlock));
+  for (size_t i = 0; i < A; ++i) {
+    const int32_t a = asks[i], spec = e->h_pod_spec[(size_t)a], pin = e->h_pod_pin[(size_t)a];
+    int settled = 0;
+    if ((size_t)spec < e->h_sflags.size() && (e->h_sflags[(size_t)spec] & YKPRED_SPEC_UNSUPPORTED)) settled = 3;
+    else if (headroom_coupled(e, spec, pre, filt)) settled = 4;
+    if (!settled && N > 0) {
+      hipLaunchKernelGGL(ykk::k_preempt_round_step, grid, dim3(ykk::kBlock), 0, st, nt, stab, vt, rs, spec, pin, limits[i], offset, pre, filt,
+                         (ykk::u64*)(d_best + i), (ykk::i64*)(d_counts + 2 * i));
+      HIPCHK(hipGetLastError());
+    }
+    if (!settled && sharded) {
+      NCCLCHK(rccl()->AllReduce(d_best + i, d_best + i, 1, ncclInt64, ncclMin, e->comm, st));
+      NCCLCHK(rccl()->AllReduce(d_counts + 2 * i, d_counts + 2 * i, 2, ncclInt64, ncclSum, e->comm, st));
+    }
+    hipLaunchKernelGGL(ykk::k_preempt_round_apply, dim3(1), dim3(ykk::kWave), 0, st, nt, stab, rs, spec, limits[i], settled, offset,
+                       (const ykk::u64*)(d_best + i), (const ykk::i64*)(d_counts + 2 * i), (ykk::i64*)(d_cells + i * B));
+    HIPCHK(hipGetLastError());
+  }
+  // (cell [2] is the owner's alone and 0 elsewhere, every other cell is the same on all ranks: one MAX makes the tables equal)
+  if (sharded) NCCLCHK(rccl()->AllReduce(d_cells, d_cells, A * B, ncclInt64, ncclMax, e->comm, st));
+  HIPCHK(hipMemcpyAsync(out_cells, d_cells, A * B * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  std::vector<int64_t> touched;
+  for (size_t i = 0; i < A; ++i) {
+    const int64_t* c = out_cells + i * B;
+    if (c[0] >= 0 && c[0] <= 4) out_summary[c[0]]++;
+    out_summary[5] += c[3];
+    if (c[1] >= 0) touched.push_back(c[1]);
+  }
+  std::sort(touched.begin(), touched.end());
+  out_summary[6] = (int64_t)(std::unique(touched.begin(), touched.end()) - touched.begin());
   return YKPRED_OK;
 }
 

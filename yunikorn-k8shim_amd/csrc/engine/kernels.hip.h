@@ -4087,6 +4087,173 @@ __global__ __launch_bounds__(kBlock) void k_preempt_victims_pod(NodeTable t, Spe
   if (live) out[n] = need;
 }
 
+// ykpred_preempt_round: victim plans for a LIST of asks, each under the state the earlier asks of the list left behind (DESIGN.md
+// §4.19). The round keeps four zeroed [n] columns beside the resident tables, which it never changes: taken = the prefix of order(n)
+// already claimed, and what the round placed on the node — request sums, pod count, wanted port words. The node a pair is evaluated on
+// with victims 0..k-1 gone (k >= taken) is still one table row away: free + cum[k-1] - placed_req, slots from count - k + placed_pods,
+// port words ports_after[k-1] | placed_ports. The overlay is constant in k, so §4.18's monotonicity holds and need' is a bisection over
+// (taken, hi], hi = max(taken, tier_end[limit-1]).
+struct PreemptRoundState {
+  int* taken;         // [n]
+  int* placed_pods;   // [n]
+  i64* placed_req;    // [R][n]
+  u64* placed_ports;  // [KP][n]
+};
+constexpr int kPreemptRoundCells = 8;
+// victim_state under the round's overlay: `nr` already carries free - placed_req and ports | placed_ports, `count` the pods placed
+__device__ __forceinline__ void round_state(const NodeTable& t, const VictimTable& vt, const NodeRegs& nr, const u64 (&placed_pt)[kMaxKP],
+                                            size_t row, i64 count, i64 allowed, int k, NodeRegs* w) {
+  victim_state(t, vt, nr, row, count, allowed, k, w);
+  if (vt.ports_after) {
+#pragma unroll
+    for (int p = 0; p < kMaxKP; ++p)
+      if (p < t.KP) w->pt[p] |= placed_pt[p];
+  }
+}
+// victim_need's sibling for a round: the FURTHER victims the pair needs beyond the `taken` already claimed on this lane's node — 0 fits
+// with those gone, extra >= 1 the shortest longer prefix, -1 never; *level as victim_need's (0 at extra 0). Every lane of the wave
+// calls it; a lane that is not live touches no memory. Rows read: base + k - 1 for k in (0, max(taken, tier_end[limit-1])], which
+// ykpred_set_victims checked (taken never passes a tier_end the round read before).
+__device__ __forceinline__ int round_need(const NodeTable& t, const SpecTable& s, const VictimTable& vt, int spec, int pin, int node, bool live,
+                                          const NodeRegs& nr, const u64 (&placed_pt)[kMaxKP], i64 count, i64 allowed, int taken, int limit,
+                                          unsigned pre_mask, unsigned filt_mask, int* level) {
+  int code = 0;
+  unsigned reason = 0;
+  *level = 0;
+  int end = taken;
+  if (live && limit > 0) end = max(taken, vt.tier_end[(size_t)(limit - 1) * t.n + node]);
+  const size_t base = live && end > 0 ? (size_t)vt.seg_base[node] : 0;
+  NodeRegs w = nr;
+  if (live && taken > 0) round_state(t, vt, nr, placed_pt, base + (size_t)taken - 1, count, allowed, taken, &w);
+  const bool fits = live && eval_pair(s, spec, pin, node, w, pre_mask, filt_mask, &code, &reason);
+  bool open = live && !fits && end > taken && reach_code_opens(code);
+  if (open) {  // with everything up to `end` gone: a lane that still fails is never
+    round_state(t, vt, nr, placed_pt, base + (size_t)end - 1, count, allowed, end, &w);
+    open = eval_pair(s, spec, pin, node, w, pre_mask, filt_mask, &code, &reason);
+  }
+  int lo = taken, hi = open ? end : taken;  // on an open lane state(lo) fails and state(hi) fits; every other lane has no interval
+  while (__ballot(hi - lo > 1)) {
+    if (hi - lo > 1) {
+      const int mid = lo + (hi - lo) / 2;
+      round_state(t, vt, nr, placed_pt, base + (size_t)mid - 1, count, allowed, mid, &w);
+      if (eval_pair(s, spec, pin, node, w, pre_mask, filt_mask, &code, &reason)) hi = mid;
+      else lo = mid;
+    }
+  }
+  if (!open) return fits ? 0 : -1;
+  int lv = 1;
+  for (int tier = 0; tier + 1 < limit; ++tier) lv += vt.tier_end[(size_t)tier * t.n + node] < hi ? 1 : 0;
+  *level = lv;
+  return hi - taken;
+}
+
+// ONE ask of the round on the grid of k_preempt_victims_pod (lane = node): the overlay columns are read coalesced, the nodes with need'
+// >= 0 are a ballot popcount, Σ extra a wave sum, the packed key (level | extra | global node: k_preempt_reach's packing, level 0 and
+// extra 0 for a node that needs no further victim) one wave MIN. The block's waves meet once in LDS; thread 0 then issues one global MIN
+// into *best and two integer adds into counts[0..1], which the host set to "no node" / zero on the stream. Nothing here writes the state.
+__global__ __launch_bounds__(kBlock) void k_preempt_round_step(NodeTable t, SpecTable s, VictimTable vt, PreemptRoundState rs, int spec, int pin,
+                                                               int limit, int node_offset, unsigned pre_mask, unsigned filt_mask,
+                                                               u64* __restrict__ best, i64* __restrict__ counts) {
+  __shared__ u64 wkey[kWavesPerBlock];
+  __shared__ i64 wsum[kWavesPerBlock];
+  __shared__ int wcnt[kWavesPerBlock];
+  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  const bool live = i < t.n;
+  const int n = live ? i : -1;
+  u64 key = ~0ull;
+  i64 sum = 0;
+  int cnt = 0;
+  if (__ballot(live)) {  // (wave-uniform: a wave wholly past N skips the work, not the barrier)
+    NodeRegs nr;
+    load_node(t, n, &nr);
+    u64 placed_pt[kMaxKP];
+#pragma unroll
+    for (int p = 0; p < kMaxKP; ++p) placed_pt[p] = 0;
+    int taken = 0;
+    i64 count = 0, allowed = 0;
+    if (live) {
+      taken = rs.taken[n];
+      count = (i64)t.count[n] + (i64)rs.placed_pods[n];
+      allowed = (i64)t.allowed[n];
+#pragma unroll
+      for (int r = 0; r < kMaxR; ++r)
+        if (r < t.R) nr.fr[r] -= rs.placed_req[(size_t)r * t.n + n];
+#pragma unroll
+      for (int p = 0; p < kMaxKP; ++p)
+        if (p < t.KP) {
+          placed_pt[p] = rs.placed_ports[(size_t)p * t.n + n];
+          nr.pt[p] |= placed_pt[p];
+        }
+      nr.slots_ok = count + 1 <= allowed;
+    }
+    int level = 0;
+    const int extra = round_need(t, s, vt, spec, pin, n, live, nr, placed_pt, count, allowed, taken, limit, pre_mask, filt_mask, &level);
+    const bool ok = live && extra >= 0;
+    cnt = __popcll(__ballot(ok));
+    if (cnt) {
+      if (ok) key = ((u64)level << kReachLevelShift) | ((u64)min((i64)extra, kReachPodsMax) << kReachPodsShift) | (u64)(unsigned)(node_offset + n);
+      sum = ok ? (i64)extra : 0;
+#pragma unroll
+      for (int off = kWave / 2; off > 0; off >>= 1) {
+        const u64 o = (u64)__shfl_xor((unsigned long long)key, off, kWave);
+        key = o < key ? o : key;
+        sum += (i64)__shfl_xor((long long)sum, off, kWave);
+      }
+    }
+  }
+  if (lane == 0) wkey[wave] = key, wsum[wave] = sum, wcnt[wave] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 1; w < kWavesPerBlock; ++w) {
+      key = wkey[w] < key ? wkey[w] : key;
+      sum += wsum[w];
+      cnt += wcnt[w];
+    }
+    if (cnt) {
+      atomicMin((unsigned long long*)best, (unsigned long long)key);
+      atomicAdd((u64*)&counts[0], (u64)cnt);
+      if (sum) atomicAdd((u64*)&counts[1], (u64)sum);
+    }
+  }
+}
+
+// The ask's turn ends here: ONE wave decodes the step's slot (the same on every rank of a sharded engine: the slot was reduced),
+// moves the four state columns of the chosen node — on the rank that owns it — with plain vector stores, and writes the ask's cells:
+// lane c keeps cell c. `settled` != 0 (3 unsupported, 4 coupled: the host decided, no step ran) writes that outcome and changes
+// nothing. Cell [2] is written by the owner alone (0 elsewhere; the host takes the MAX over the ranks).
+__global__ __launch_bounds__(kWave) void k_preempt_round_apply(NodeTable t, SpecTable s, PreemptRoundState rs, int spec, int limit, int settled,
+                                                               int node_offset, const u64* __restrict__ best, const i64* __restrict__ counts,
+                                                               i64* __restrict__ cells) {
+  const int lane = threadIdx.x;
+  i64 outcome = settled, node = -1, from = 0, extra = 0, level = 0, open = 0, total = 0;
+  if (!settled) {
+    const u64 key = *best;
+    const i64 lv = (i64)(key >> kReachLevelShift);
+    open = counts[0];
+    total = counts[1];
+    outcome = 2;
+    if (lv <= kReachMaxTiers) {
+      level = lv;
+      node = (i64)(key & 0x7fffffffull);
+      extra = (i64)((key >> kReachPodsShift) & (u64)kReachPodsMax);
+      outcome = extra > 0 ? 1 : 0;
+      const i64 local = node - node_offset;
+      if (local >= 0 && local < t.n) {
+        from = rs.taken[local];
+        const int pods = rs.placed_pods[local];
+        if (lane == 0) rs.taken[local] = (int)(from + extra), rs.placed_pods[local] = pods + 1;
+        if (lane < t.R) rs.placed_req[(size_t)lane * t.n + local] += s.req[(size_t)spec * s.R + lane];
+        if (lane < t.KP) rs.placed_ports[(size_t)lane * t.n + local] |= s.wanted_ports[(size_t)spec * s.KP + lane];
+      }
+    }
+  }
+  const i64 mine = lane == 0 ? outcome : lane == 1 ? node : lane == 2 ? from : lane == 3 ? extra : lane == 4 ? level : lane == 5 ? (i64)limit
+                   : lane == 6 ? open : total;
+  if (lane < kPreemptRoundCells) cells[lane] = mine;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Conflict-resolved decisions: the SEQUENTIAL loop yunikorn-core drives through the shim. For the asks of a
 // round, in order: the first node of the bin-pack order — under the state the EARLIER asks of the round left behind — that

@@ -4143,6 +4143,141 @@ int32_t ykhost_preempt_victims_by_key(ykhost_t* h, const char* allocation_key, i
   return 0;
 }
 
+// ---- preemption round (ykpred_preempt_round) -----------------------------------------------------------------------------------------
+namespace {
+// order(node)[from .. from + count): the uids, each followed by one NUL, appended at buf + *used as long as whole uids fit; *used grows by
+// what the slice needs either way. → the number of pods in the slice. The mirror alone answers it.
+int32_t victim_uid_range(const ykhost* h, int node, int64_t from, int64_t count, char* buf, int64_t len, int64_t* used) {
+  std::vector<const Pod*> order;
+  victim_order(h, *h->nodes[(size_t)node], &order);
+  int32_t got = 0;
+  for (int64_t i = std::max<int64_t>(from, 0); i < (int64_t)order.size() && got < count; ++i, ++got) {
+    const std::string& uid = order[(size_t)i]->uid;
+    if (buf && *used + (int64_t)uid.size() + 1 <= len) memcpy(buf + *used, uid.c_str(), uid.size() + 1);
+    *used += (int64_t)uid.size() + 1;
+  }
+  return got;
+}
+}  // namespace
+
+int32_t ykhost_victim_range(ykhost_t* h, int32_t node, int32_t from, int32_t count, char* uids_buf, int64_t len, int32_t* got, int64_t* needed) {
+  YKHOST_LOCKED(h);
+  if (!got || len < 0 || from < 0 || count < 0) return fail(h, "victim_range: bad argument", -1);
+  *got = 0;
+  if (h->rc_bounds.empty()) return fail(h, "victim_range: no preemption tiers (ykhost_set_preemption_tiers)", YKPRED_E_STATE);
+  if (node < 0 || (size_t)node >= h->nodes.size()) return fail(h, "victim_range: node index out of range", YKPRED_E_INVALID);
+  int64_t used = 0;
+  *got = victim_uid_range(h, node, from, count, uids_buf, len, &used);
+  if (needed) *needed = used;
+  return 0;
+}
+
+int32_t ykhost_preempt_round(ykhost_t* h, int32_t n, const int32_t* asks, int64_t* out_cells, int64_t* out_summary) {
+  YKHOST_LOCKED(h);
+  constexpr size_t B = YKPRED_PREEMPT_ROUND_CELLS;
+  if (n < 0 || !out_summary || (n > 0 && !out_cells)) return fail(h, "preempt_round: bad argument", -1);
+  int rc = victims_sync(h, "preempt_round");
+  if (rc) return rc;
+  int32_t world = 1;
+  ykpred_comm_info(h->eng, nullptr, &world, nullptr);
+  const int P = (int)h->pending.size();
+  for (int i = 0; i < n; ++i)
+    if ((asks ? asks[i] : i) < 0 || (asks ? asks[i] : i) >= P) return fail(h, "preempt_round: ask index out of range", YKPRED_E_INVALID);
+  // (an ask routed to the CPU manager is settled here and changes nothing; on a node-sharded handle every ask goes to the engine)
+  std::vector<int32_t> list, limits, slot;
+  int64_t routed = 0;
+  for (int i = 0; i < n; ++i) {
+    const int row = asks ? asks[i] : i;
+    const Pod* p = h->pending[(size_t)row];
+    int64_t* c = out_cells + (size_t)i * B;
+    if (world <= 1 && h->enc.unsupported.count(p->tpl)) {
+      std::fill(c, c + B, (int64_t)0);
+      c[0] = 3;
+      c[1] = -1;
+      c[5] = reclaim_limit(h, p);
+      routed++;
+    } else {
+      list.push_back(row);
+      limits.push_back(reclaim_limit(h, p));
+      slot.push_back(i);
+    }
+  }
+  std::vector<int64_t> rows(list.size() * B + 1);
+  rc = ykpred_preempt_round(h->eng, (int32_t)list.size(), list.data(), limits.data(), h->alloc_pre, h->alloc_filt, rows.data(), out_summary);
+  if (rc) return fail(h, std::string("ykpred_preempt_round: ") + ykpred_last_error(h->eng), rc);
+  out_summary[3] += routed;
+  for (size_t k = 0; k < list.size(); ++k) memcpy(out_cells + (size_t)slot[k] * B, rows.data() + k * B, B * sizeof(int64_t));
+  return 0;
+}
+
+namespace {
+// the ask row behind an allocation key, for the by-keys calls of the round (a routed ask keeps its row: the round settles it as outcome 3)
+int round_row_by_key(ykhost* h, const char* allocation_key, const Pod** pod) {
+  const std::string key = allocation_key ? allocation_key : "";
+  auto it = h->by_uid.find(key);
+  if (it == h->by_uid.end()) return fail(h, "preempt_round_by_keys: no such pod: " + key, YKHOST_E_POD_NOT_FOUND);
+  if (!it->second->ask) return fail(h, "pod holds no ask row", YKHOST_E_NOT_AN_ASK);
+  *pod = it->second;
+  return 0;
+}
+// The round over ask rows, then per ask the node by name and the uids order(node)[from .. from + extra).
+int round_names_and_uids(ykhost* h, int32_t n, const int32_t* rows, int64_t* out_cells, int64_t* out_summary, char* node_names, int64_t names_len,
+                         char* victim_uids_buf, int64_t uids_len, int64_t* needed2) {
+  constexpr size_t B = YKPRED_PREEMPT_ROUND_CELLS;
+  int rc = ykhost_preempt_round(h, n, rows, out_cells, out_summary);
+  if (rc) return rc;
+  int32_t offset = 0;
+  ykpred_comm_info(h->eng, nullptr, nullptr, &offset);
+  int64_t names_used = 0, uids_used = 0;
+  for (int i = 0; i < n; ++i) {
+    const int64_t* c = out_cells + (size_t)i * B;
+    const int64_t local = c[1] - offset;
+    const bool here = c[1] >= 0 && local >= 0 && local < (int64_t)h->nodes.size();  // ("" and nothing for a node on another shard)
+    const std::string name = here ? h->nodes[(size_t)local]->node.name : std::string();
+    if (node_names && names_used + (int64_t)name.size() + 1 <= names_len) memcpy(node_names + names_used, name.c_str(), name.size() + 1);
+    names_used += (int64_t)name.size() + 1;
+    if (here && c[3] > 0) victim_uid_range(h, (int)local, c[2], c[3], victim_uids_buf, uids_len, &uids_used);
+  }
+  if (needed2) needed2[0] = names_used, needed2[1] = uids_used;
+  return 0;
+}
+}  // namespace
+
+// The list named as the core names it, one crossing: the cells, and per ask the node by name and its victims by uid.
+int32_t ykhost_preempt_round_by_keys(ykhost_t* h, int32_t n, const char* const* allocation_keys, int64_t* out_cells, int64_t* out_summary,
+                                     char* node_names, int64_t names_len, char* victim_uids_buf, int64_t uids_len, int64_t* needed2) {
+  YKHOST_LOCKED(h);
+  if (n < 0 || !out_summary || (n > 0 && (!allocation_keys || !out_cells)) || names_len < 0 || uids_len < 0)
+    return fail(h, "preempt_round_by_keys: bad argument", -1);
+  if (needed2) needed2[0] = needed2[1] = 0;
+  if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
+  ensure_uid_index(h);
+  std::vector<const Pod*> pods((size_t)n + 1, nullptr);
+  for (int i = 0; i < n; ++i)
+    if (int rc = round_row_by_key(h, allocation_keys[i], &pods[(size_t)i])) return rc;
+  int rc = sync(h);  // (rows are assigned by the sync; the pods stay where they are)
+  if (rc) return rc;
+  std::vector<int32_t> rows((size_t)n + 1);
+  for (int i = 0; i < n; ++i) rows[(size_t)i] = pods[(size_t)i]->row;
+  return round_names_and_uids(h, n, rows.data(), out_cells, out_summary, node_names, names_len, victim_uids_buf, uids_len, needed2);
+}
+
+int32_t ykhost_preempt_gang_by_key(ykhost_t* h, const char* allocation_key, int32_t want, int64_t* out_cells, int64_t* out_summary, char* node_names,
+                                   int64_t names_len, char* victim_uids_buf, int64_t uids_len, int64_t* needed2) {
+  YKHOST_LOCKED(h);
+  if (want < 0 || !out_summary || (want > 0 && !out_cells) || names_len < 0 || uids_len < 0) return fail(h, "preempt_gang_by_key: bad argument", -1);
+  if (needed2) needed2[0] = needed2[1] = 0;
+  if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
+  ensure_uid_index(h);
+  const Pod* pod = nullptr;  // (the key is resolved once: every copy is the same row)
+  int rc = round_row_by_key(h, allocation_key, &pod);
+  if (rc) return rc;
+  rc = sync(h);
+  if (rc) return rc;
+  std::vector<int32_t> rows((size_t)want + 1, pod->row);
+  return round_names_and_uids(h, want, rows.data(), out_cells, out_summary, node_names, names_len, victim_uids_buf, uids_len, needed2);
+}
+
 // ---- headroom per topology domain (ykpred_headroom_groups) --------------------------------------------------------------------------
 // The groups of a label key: ids are the ranks of the bytewise-sorted distinct values, a node without the label gets -1. The column is
 // kept per (key, node-table epoch). On a node-sharded handle the value lists of the shards are united first (lengths, then the lists

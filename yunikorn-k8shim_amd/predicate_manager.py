@@ -68,6 +68,12 @@ PREEMPT_HEADROOM_STATUS, PREEMPT_HEADROOM_LIMIT, PREEMPT_HEADROOM_WANT, PREEMPT_
 # over the nodes of [1], 0 ...
 VICTIM_CELLS = 16
 VICTIM_FIT, VICTIM_OPEN, VICTIM_NEVER, VICTIM_STATUS, VICTIM_LIMIT, VICTIM_BEST_LEVEL, VICTIM_BEST_NODE, VICTIM_BEST_NEED, VICTIM_TOTAL = range(9)
+# ykpred_preempt_round: per ask of the list int64[PREEMPT_ROUND_CELLS] = outcome (0 placed with no further victim, 1 placed by preemption,
+# 2 nowhere, 3 routed, 4 coupled), node (global index, -1: none), from (the node's prefix already claimed), extra (further victims),
+# level, the ask's limit, nodes that could take the ask at its turn, the sum of extra over those that need victims
+PREEMPT_ROUND_CELLS = 8
+(PREEMPT_ROUND_OUTCOME, PREEMPT_ROUND_NODE, PREEMPT_ROUND_FROM, PREEMPT_ROUND_EXTRA, PREEMPT_ROUND_LEVEL, PREEMPT_ROUND_LIMIT, PREEMPT_ROUND_OPEN,
+ PREEMPT_ROUND_TOTAL) = range(8)
 
 
 def plugin_mask(names):
@@ -921,6 +927,78 @@ class GpuPredicateManager:
         self._check(rc)
         victims = [u.decode() for u in uids.raw.split(b"\0")[:int(out[VICTIM_BEST_NEED])] if u] if name.value else []
         return out, name.value.decode(), victims
+
+    # ---- preemption round: conflict-resolved victim plans for a list of asks ----------------------------------------------
+    def preempt_round(self, pods=None, pre_mask=None, filt_mask=None):
+        """Victim plans for a LIST of asks, each under the state the earlier asks of the list left behind (ykpred_preempt_round) →
+        (np.int64[n, PREEMPT_ROUND_CELLS], np.int64[8] summary = asks per outcome 0..4, victims in all, distinct nodes touched, 0).
+        pods: ask indices or UIDs IN ORDER, a repeat is one more copy; None = every ask in index order. The victims of ask i are
+        victim_range(node, from, extra). Nothing in the mirror or on the device changes; two calls in a row give equal answers.
+        Explicit masks go to the engine with the limits the host derives."""
+        if pods is None:
+            count, ptr = self.num_pods, None
+        else:
+            idx = [p if isinstance(p, (int, np.integer)) else self.pod_index(p) for p in pods]
+            arr = np.ascontiguousarray(idx, dtype=np.int32)
+            count, ptr = len(arr), arr.ctypes.data
+        out = np.zeros((max(count, 1), PREEMPT_ROUND_CELLS), dtype=np.int64)
+        summary = np.zeros(8, dtype=np.int64)
+        if pre_mask is None and filt_mask is None:
+            self._check(self._L.ykhost_preempt_round(self._h, count, ptr, out.ctypes.data, summary.ctypes.data))
+        else:
+            pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
+            self.victim_table(planes=False)   # (syncs the tables, the reclaim and the victim table)
+            limits = np.zeros(max(count, 1), dtype=np.int32)
+            self._check(self._L.ykhost_preempt_limits(self._h, count, ptr, limits.ctypes.data))
+            if ptr is None:
+                arr = np.arange(count, dtype=np.int32)
+                ptr = arr.ctypes.data
+            self._pcheck(self._P.ykpred_preempt_round(self.engine, count, ptr, limits.ctypes.data, pre, filt, out.ctypes.data, summary.ctypes.data))
+        return out[:count].copy(), summary
+
+    def _round_by_keys(self, call, count):
+        names_len, uids_len = 64 * count + 256, 64 * count + (1 << 12)
+        while True:
+            out = np.zeros((max(count, 1), PREEMPT_ROUND_CELLS), dtype=np.int64)
+            summary = np.zeros(8, dtype=np.int64)
+            need = np.zeros(2, dtype=np.int64)
+            names, uids = C.create_string_buffer(names_len), C.create_string_buffer(uids_len)
+            rc = call(out.ctypes.data, summary.ctypes.data, C.addressof(names), names_len, C.addressof(uids), uids_len, need.ctypes.data)
+            if rc in (-10, -12):
+                raise KeyError(self._L.ykhost_last_error(self._h).decode())
+            self._check(rc)
+            if need[0] <= names_len and need[1] <= uids_len:
+                break
+            names_len, uids_len = int(need[0]) + 1, int(need[1]) + 1   # (the round starts from zero state each call: asking again is exact)
+        node = [u.decode() for u in names.raw[:int(need[0])].split(b"\0")[:count]]
+        flat = [u.decode() for u in uids.raw[:int(need[1])].split(b"\0")[:-1]]
+        victims, at = [], 0
+        for i in range(count):
+            k = int(out[i, PREEMPT_ROUND_EXTRA]) if node[i] else 0
+            victims.append(flat[at:at + k])
+            at += k
+        return out[:count].copy(), summary, node, victims
+
+    def preempt_round_by_keys(self, uids):
+        """The round for asks named by allocation key, ONE crossing (ykhost_preempt_round_by_keys) → (cells, summary, node names — "" where
+        the ask went nowhere —, per ask the uids of its victims order(node)[from .. from + extra)). KeyError for a key that names no ask."""
+        keys = [u.encode() for u in uids]
+        arr = (C.c_char_p * max(len(keys), 1))(*keys)
+        return self._round_by_keys(lambda *a: self._L.ykhost_preempt_round_by_keys(self._h, len(keys), C.addressof(arr), *a), len(keys))
+
+    def preempt_gang(self, uid, want):
+        """`want` copies of one ask as a round (ykhost_preempt_gang_by_key): where each copy goes and at whose cost → as
+        preempt_round_by_keys. summary[0] + summary[1] == min(want, preempt_headroom copies at the ask's limit)."""
+        return self._round_by_keys(lambda *a: self._L.ykhost_preempt_gang_by_key(self._h, uid.encode(), int(want), *a), int(want))
+
+    def victim_range(self, node, start, count):
+        """The uids of order(node)[start .. start + count) (ykhost_victim_range; works without a device)."""
+        n = node if isinstance(node, (int, np.integer)) else self.node_index(node)
+        got, need = C.c_int32(0), C.c_int64(0)
+        self._check(self._L.ykhost_victim_range(self._h, int(n), int(start), int(count), None, 0, C.addressof(got), C.addressof(need)))
+        buf = C.create_string_buffer(need.value + 1)
+        self._check(self._L.ykhost_victim_range(self._h, int(n), int(start), int(count), C.addressof(buf), need.value + 1, C.addressof(got), C.addressof(need)))
+        return [u.decode() for u in buf.raw[:need.value].split(b"\0")[:got.value]]
 
     def victim_table(self, planes=True):
         """The victim table as the mirror keeps it — patched segment by segment, not derived afresh (ykhost_victim_table; works
