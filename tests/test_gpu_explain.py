@@ -291,6 +291,65 @@ def test_node_sharded_engines_return_cluster_wide_bins(tmp_path, world, total_no
     assert out.stdout.count("rccl-stub: explain True sums True mismatch True") == world, (out.stdout[-1500:], out.stderr[-1500:])
 
 
+def tiered_engine():
+    """The generated cluster of the two-shard case on one engine, three residents per node — one per tier, every fourth node
+    over-committed until victims go — the reclaim and the victim table over three tiers, and 70 asks of 70 distinct request vectors:
+    a list of k of them is k tasks, whatever the generator's templates share."""
+    m = pkg.GpuPredicateManager()
+    m.generate_kwok(seed=0x59554E49 + 123, num_nodes=333, num_pods=600, num_templates=40, node_affinity=1, spread=1)
+    names = [json.loads(line)["metadata"]["name"] for line in m.dump_documents(0).splitlines() if line]
+    assert len(names) == 333
+    docs = []
+    for n, name in enumerate(names):
+        for t, prio in enumerate((-300, -200, -100)):
+            cpu, mem = (300 + 100 * t) * (8 if n % 4 == 0 else 1), (1 + t) << (33 if n % 4 == 0 else 28)
+            docs.append({"metadata": {"name": f"tier{t}-{n}", "uid": f"tier{t}-{n}", "namespace": "shared", "labels": {"app": "tiered"}},
+                         "spec": {"nodeName": name, "priority": prio, "containers": [{"name": "c", "resources": {"requests": {"cpu": f"{cpu}m", "memory": str(mem)}}}]},
+                         "status": {"phase": "Running"}})
+    for i in range(70):
+        docs.append({"metadata": {"name": f"own-{i}", "uid": f"own-{i}", "namespace": "shared"},
+                     "spec": {"containers": [{"name": "c", "resources": {"requests": {"cpu": f"{100 + 150 * i}m", "memory": str((1 + i % 5) << 28)}}}],
+                              "tolerations": [{"key": "kwok.x-k8s.io/node", "operator": "Exists", "effect": "NoSchedule"}]},   # (every node carries it)
+                     "status": {"phase": "Pending"}})
+    assert m.update_pods_batch(docs) == len(docs)
+    m.set_preemption_tiers((-250, -150, -50))
+    return m, np.array([m.pod_index(f"own-{i}") for i in range(70)], dtype=np.int32)
+
+
+QUERIES = {"explain": lambda m, asks: m.explain(asks), "headroom": lambda m, asks: m.headroom(asks), "preempt_reach": lambda m, asks: m.preempt_reach(asks),
+           "preempt_headroom": lambda m, asks: m.preempt_headroom(asks, wants=[3] * len(asks)), "preempt_victims": lambda m, asks: m.preempt_victims(asks)}
+
+
+def test_the_five_reduce_calls_share_one_table_buffer():
+    """ykpred_explain, _headroom, _preempt_reach, _preempt_headroom and _preempt_victims carve their tables out of ONE engine buffer.
+    Back to back on one engine with lists of 70 tasks, then 1, then 33 — both sides of the 32-task chunk, the buffer in use shrinking
+    inside a block that does not — and again on a second engine in another order: every result equals, bit for bit, the same call on a
+    fresh engine that makes no other call (one per call; its lists grow — 1, 33, 70 tasks — so each runs in a block allocated for it)."""
+    want, lists = {}, {}
+    for name, query in QUERIES.items():   # the references, computed once
+        m, own = tiered_engine()
+        try:
+            lists = {1: np.array([5, 5, 5], dtype=np.int32), 33: own[:36:-1].copy(), 70: own}
+            assert [len(set(v.tolist())) for v in lists.values()] == [1, 33, 70]
+            for k, asks in lists.items():
+                want[name, k] = query(m, asks).copy()
+        finally:
+            m.close()
+    distinct = {name: len({tuple(r) for r in want[name, 70].tolist()}) for name in QUERIES}
+    assert min(distinct.values()) > 8, distinct
+    assert want["preempt_reach", 70][:, 1:4].sum() > 0 and want["preempt_victims", 70][:, 1].sum() > 0   # (the tiers open nodes: the tables are read)
+    orders = ([(name, k) for k in (70, 1, 33) for name in QUERIES],            # list by list, the five calls on each
+              [(name, k) for name in reversed(list(QUERIES)) for k in (70, 1, 33)])  # call by call, the last first
+    for order in orders:
+        m, _ = tiered_engine()
+        try:
+            for step, (name, k) in enumerate(order):
+                got = QUERIES[name](m, lists[k])
+                assert got.dtype == want[name, k].dtype and np.array_equal(got, want[name, k]), (step, name, k, np.flatnonzero((got != want[name, k]).any(axis=1))[:5])
+        finally:
+            m.close()
+
+
 def test_at_configs2_size(pm):
     """50 000 nodes x 1 000 000 asks (seeded as scripts/bench_query.py seeds it): one representative of every class explained in
     one call; 64 of them, drawn by a fixed seed, equal ykpred_query_pod_packed aggregated in numpy; bins [0..10] sum to N for all."""

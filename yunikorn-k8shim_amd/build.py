@@ -15,8 +15,8 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 LIB = os.path.join(PKG, "lib")
 ENGINE_SRC = os.path.join(PKG, "csrc", "engine", "engine.hip")
-ENGINE_DEPS = [ENGINE_SRC, os.path.join(PKG, "csrc", "engine", "kernels.hip.h"),
-               os.path.join(PKG, "csrc", "engine", "preempt_headroom_finish.h"), os.path.join(ROOT, "include", "ykpred.h")]
+ENGINE_DEPS = [ENGINE_SRC] + [os.path.join(PKG, "csrc", "engine", f) for f in ("kernels.hip.h", "ask_tasks.h", "preempt_headroom_finish.h")] + [
+    os.path.join(ROOT, "include", "ykpred.h")]
 HOST_SRC = os.path.join(PKG, "csrc", "host", "host.cpp")
 HOST_DEPS = [HOST_SRC] + [os.path.join(PKG, "csrc", "host", f) for f in ("encoder.h", "objects.h", "minijson.h", "quantity.h", "jsonscan.h")] + [
     os.path.join(ROOT, "include", "ykhost.h"), os.path.join(ROOT, "include", "ykpred.h")]

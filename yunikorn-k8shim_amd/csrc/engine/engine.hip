@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "kernels.hip.h"
+#include "ask_tasks.h"
 #include "preempt_headroom_finish.h"
 
 using ykk::i64;
@@ -275,17 +276,18 @@ struct ykpred_engine {
   int sweep_rows[ykk::kMaxIdxRows] = {0, 0}, sweep_row_off[ykk::kMaxIdxRows + 1] = {0, 0, 0}, sweep_runs = 0;  // per walked dimension
   int index_rows_needed = 0;         // index rows some class OUTSIDE the sweep runs reads (the full pass walks only those)
   DevBuf d_agree;  // sharded rounds: what the ranks agree on before the first batch
-  DevBuf d_explain;  // ykpred_explain: task specs | task pins | [tasks][YKPRED_EXPLAIN_BINS] counts
-  DevBuf d_headroom;  // ykpred_headroom: [tasks][YKPRED_HEADROOM_CELLS] cells | [tasks] max replicas | task specs | task pins
+  // The one table of the per-ask reduce calls (ask_query_run): [tasks][B] cells | [tasks] side column | task specs | task pins | task
+  // limits. ykpred_explain: B = YKPRED_EXPLAIN_BINS int32 counts, no side column, no limits; ykpred_headroom: YKPRED_HEADROOM_CELLS
+  // int64 cells, the max replicas beside them; ykpred_preempt_reach / _victims: YKPRED_REACH_CELLS / YKPRED_VICTIM_CELLS cells, the best
+  // keys beside them, limits; ykpred_preempt_headroom: YKPRED_PREEMPT_HEADROOM_CELLS per-level deltas, limits. One buffer serves all: the
+  // engine admits one call at a time and each call ends in a synchronise.
+  DevBuf d_query;
   DevBuf d_groups;  // ykpred_headroom_groups: summaries | pair wants | pair tasks | task specs | task pins | coupled | node groups | one table chunk
   DevBuf d_domain_head;  // headroom_domains_run (ykpred_headroom_spread, _affinity): summaries | tasks | one table chunk (rows | extra cells)
-  DevBuf d_reach;  // ykpred_preempt_reach: [tasks][YKPRED_REACH_CELLS] cells | [tasks] best keys | task specs | task pins | task limits
-                   // ykpred_preempt_headroom: [tasks][YKPRED_PREEMPT_HEADROOM_CELLS] per-level deltas | task specs | task pins | task limits
   // the resident reclaim table (ykpred_set_reclaim): what the pods of each priority tier give back per node
   DevBuf d_rc_req, d_rc_pods, d_rc_ports;  // [T][R][N] i64; [T][N] int; [T][KP][N] u64 (only with rc_ports)
   int rc_tiers = 0;                        // 0 = no table
   bool rc_ports = false;
-  DevBuf d_victims;  // ykpred_preempt_victims: [tasks][YKPRED_VICTIM_CELLS] cells | [tasks] best keys | task specs | task pins | task limits
   // the resident victim table (ykpred_set_victims): one row per eligible pod, one segment per node in (priority, uid) order
   DevBuf d_vt_base, d_vt_tier_end, d_vt_cum, d_vt_ports;  // [N] int; [T][N] int; [R][P] i64; [KP][P] u64 (only with vt_ports)
   std::vector<int32_t> h_vt_base, h_vt_cap;               // the segments, kept for ykpred_update_victims_node
@@ -1791,7 +1793,7 @@ void ykpred_destroy(ykpred_engine_t* e) {
                     &e->d_member_key, &e->d_name_rank, &e->d_member_tie, &e->d_class_rows_all, &e->d_gathered_classes, &e->d_class_rows_slot,
                     &e->d_class_sig_ident, &e->d_expand_count, &e->d_layout_hash, &e->d_gathered_pod_class, &e->d_row_pod,
                     &e->d_round, &e->d_fx_off, &e->d_fx_cls, &e->d_fx_cnt, &e->d_fx_occ, &e->d_sp_sig_of, &e->d_class_list_b, &e->d_gathered, &e->d_gathered_map,
-                    &e->d_xkey, &e->d_xcand, &e->d_reach, &e->d_rc_req, &e->d_rc_pods, &e->d_rc_ports, &e->d_victims,
+                    &e->d_xkey, &e->d_xcand, &e->d_query, &e->d_groups, &e->d_domain_head, &e->d_rc_req, &e->d_rc_pods, &e->d_rc_ports,
                     &e->d_vt_base, &e->d_vt_tier_end, &e->d_vt_cum, &e->d_vt_ports, &e->d_pround})
     b->release();
   if (e->ev_ready)
@@ -4436,135 +4438,6 @@ int32_t ykpred_query_pod(ykpred_engine_t* e, int32_t pod, uint32_t pre, uint32_t
   return YKPRED_OK;
 }
 
-// ykpred_query_pod with ONE 4-byte word per node and one device → host copy: bits 0-7 plugin code, bit 8 fit, bits 9-12 the
-// four reason flags, bits 13.. the insufficient-resource flags (reason >> YKPRED_REASON_RESOURCE_SHIFT).
-int32_t ykpred_query_pod_packed(ykpred_engine_t* e, int32_t pod, uint32_t pre, uint32_t filt, uint32_t* out) {
-  YK_SERIALISE(e);
-  Range roctx_range("ykpred:query_pod");
-  if (e) e->n_queries++;
-  if (!e || !out) return fail(e, YKPRED_E_INVALID, "query_pod_packed: bad argument");
-  if (!e->nodes_set || !e->specs_set || !e->pods_set) return fail(e, YKPRED_E_STATE, "query_pod_packed: tables not uploaded");
-  if (pod < 0 || pod >= e->P) return fail(e, YKPRED_E_INVALID, "query_pod_packed: index out of range");
-  if (e->N == 0) return YKPRED_OK;
-  HIPCHK(hipSetDevice(e->cfg.device));
-  hipStream_t st = e->own_stream;
-  if ((pre & filt & (YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD | YKPRED_PLUGIN_INTER_POD_AFFINITY))) TRY(ensure_histograms(e, st));
-  else if (e->spread_dirty) TRY(build_spread_tables(e, st));
-  const size_t N = (size_t)e->N;
-  HIPCHK(e->d_scratch.ensure(N * sizeof(uint32_t) + 64));
-  hipLaunchKernelGGL(ykk::k_query_pod_packed, dim3((unsigned)((N + ykk::kBlock - 1) / ykk::kBlock)), dim3(ykk::kBlock), 0, st, node_table(e),
-                     spec_table(e), e->h_pod_spec[(size_t)pod], e->h_pod_pin[(size_t)pod], pre, filt, e->d_scratch.as<uint32_t>());
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, e->d_scratch.p, N * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return YKPRED_OK;
-}
-
-// Why an ask fits nowhere: the histogram of ykpred_query's verdicts over every node, reduced on the device (k_explain). Reads the
-// tables only — no bitmap, no evaluation state is consulted or changed.
-int32_t ykpred_explain(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, uint32_t pre, uint32_t filt, int32_t* out) {
-  YK_SERIALISE(e);
-  Range roctx_range("ykpred:explain");
-  if (e) e->n_queries++;
-  static_assert(ykk::kExplainBins == YKPRED_EXPLAIN_BINS, "k_explain writes the layout of ykpred.h");
-  constexpr size_t B = YKPRED_EXPLAIN_BINS;
-  if (!e) return YKPRED_E_INVALID;
-  const bool sharded = e->comm && e->comm_world > 1;
-  int rc = YKPRED_OK;
-  const char* why = "";
-  if (n_asks < 0 || (n_asks > 0 && (!asks || !out))) rc = YKPRED_E_INVALID, why = "explain: bad argument";
-  else if (!e->nodes_set || !e->specs_set || !e->pods_set) rc = YKPRED_E_STATE, why = "explain: tables not uploaded";
-  else
-    for (int i = 0; i < n_asks; ++i)
-      if (asks[i] < 0 || asks[i] >= e->P) rc = YKPRED_E_INVALID, why = "explain: index out of range";
-  if (!sharded && rc != YKPRED_OK) return fail(e, rc, why);
-  if (!sharded && n_asks == 0) return YKPRED_OK;
-  // Tasks: the distinct (spec, pin) of the list, numbered by first appearance; task_of[i] is ask i's row of the table. A sharded engine
-  // cannot key on the pin (a node index of ITS shard): an ask with a NodeName is a task of its own there, and with by_ask every
-  // distinct ask index is — the keys every rank derives alike whatever its own spec table merges.
-  std::vector<int32_t> task_of, t_spec, t_pin;
-  auto build_tasks = [&](bool by_ask) {
-    std::unordered_map<u64, int32_t> index;
-    task_of.assign((size_t)n_asks, 0);
-    t_spec.clear();
-    t_pin.clear();
-    for (int i = 0; i < n_asks; ++i) {
-      const int32_t a = asks[i], sp = e->h_pod_spec[(size_t)a], pin = e->h_pod_pin[(size_t)a];
-      u64 key = ((u64)(uint32_t)sp << 32) | (u64)(uint32_t)pin;
-      if (by_ask || (sharded && pin != YKPRED_NO_NODE_NAME)) key = (1ull << 63) | (u64)(uint32_t)a;
-      auto it = index.emplace(key, (int32_t)t_spec.size());
-      if (it.second) {
-        t_spec.push_back(sp);
-        t_pin.push_back(pin);
-      }
-      task_of[(size_t)i] = it.first->second;
-    }
-  };
-  if (rc == YKPRED_OK) build_tasks(false);
-  HIPCHK(hipSetDevice(e->cfg.device));
-  hipStream_t st = e->own_stream;
-  if (rc == YKPRED_OK && e->N > 0 && n_asks > 0) {
-    // (the histogram preparation of ykpred_query; on a sharded engine a stale histogram is a status the ranks agree on below)
-    if ((pre & filt & (YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD | YKPRED_PLUGIN_INTER_POD_AFFINITY))) rc = ensure_histograms(e, st);
-    else if (e->spread_dirty) rc = build_spread_tables(e, st);
-    if (rc != YKPRED_OK && !sharded) return rc;
-  }
-  if (sharded) {
-    // Collective: the ranks agree on (status, ask count, list, task partition) before anybody enters the reduce — a rank that cannot
-    // run, or a different list, is the SAME error on every rank. Partitions that differ (per-shard dictionaries merge specs
-    // differently) are no error: every rank then takes one task per distinct ask.
-    struct Agree {
-      int32_t rc, n;
-      u64 list, partition;
-    };
-    Agree mine{rc, n_asks, 0x9e3779b97f4a7c15ull, 0x9e3779b97f4a7c15ull};
-    if (rc == YKPRED_OK)
-      for (int i = 0; i < n_asks; ++i) {
-        mine.list = (mine.list ^ (u64)(uint32_t)asks[i]) * 0x100000001b3ull;
-        mine.partition = (mine.partition ^ (u64)(uint32_t)task_of[(size_t)i]) * 0x100000001b3ull;
-      }
-    const int W = e->comm_world;
-    HIPCHK(e->d_agree.ensure((size_t)(W + 1) * sizeof(Agree)));
-    Agree* d = e->d_agree.as<Agree>();
-    HIPCHK(hipMemcpyAsync(d + W, &mine, sizeof(Agree), hipMemcpyHostToDevice, st));
-    NCCLCHK(rccl()->AllGather(d + W, d, sizeof(Agree), ncclInt8, e->comm, st));
-    std::vector<Agree> all((size_t)W);
-    HIPCHK(hipMemcpyAsync(all.data(), d, (size_t)W * sizeof(Agree), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (int g = 0; g < W; ++g)
-      if (all[(size_t)g].rc != YKPRED_OK)
-        return fail(e, all[(size_t)g].rc, "explain (sharded): rank " + std::to_string(g) + " cannot run the call (" +
-                                              (g == e->comm_rank && *why ? why : "bad argument, tables not uploaded, an index out of range or stale topology histograms") +
-                                              "): no rank runs it");
-    for (int g = 0; g < W; ++g)
-      if (all[(size_t)g].n != all[0].n || all[(size_t)g].list != all[0].list)
-        return fail(e, YKPRED_E_INVALID, "explain (sharded): rank " + std::to_string(g) + " was handed a different ask list: every rank passes the same asks");
-    if (n_asks == 0) return YKPRED_OK;
-    bool same = true;
-    for (int g = 0; g < W; ++g) same = same && all[(size_t)g].partition == all[0].partition;
-    if (!same) build_tasks(true);
-  }
-  const size_t T = t_spec.size();
-  HIPCHK(e->d_explain.ensure(T * (2 * sizeof(int32_t) + B * sizeof(int32_t)) + 64));
-  int32_t* d_bins = e->d_explain.as<int32_t>();  // (the table first: what the reduce and the copy move)
-  int32_t* d_spec = d_bins + T * B;
-  int32_t* d_pin = d_spec + T;
-  HIPCHK(hipMemsetAsync(d_bins, 0, T * B * sizeof(int32_t), st));
-  if (e->N > 0) {
-    HIPCHK(hipMemcpyAsync(d_spec, t_spec.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_pin, t_pin.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    const dim3 grid((unsigned)((T + ykk::kExplainTasks - 1) / ykk::kExplainTasks), (unsigned)((e->N + ykk::kBlock - 1) / ykk::kBlock));
-    hipLaunchKernelGGL(ykk::k_explain, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e), (int)T, d_spec, d_pin, pre, filt, d_bins);
-    HIPCHK(hipGetLastError());
-  }
-  if (sharded) NCCLCHK(rccl()->AllReduce(d_bins, d_bins, T * B, ncclInt32, ncclSum, e->comm, st));
-  std::vector<int32_t> rows(T * B);
-  HIPCHK(hipMemcpyAsync(rows.data(), d_bins, T * B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  for (int i = 0; i < n_asks; ++i) memcpy(out + (size_t)i * B, rows.data() + (size_t)task_of[(size_t)i] * B, B * sizeof(int32_t));
-  return YKPRED_OK;
-}
-
 // Copies of an ask are COUPLED when its verdicts read the topology histograms — the condition under which eval_pair enters
 // constraints_fail: a placed copy then changes the verdicts of the next one on other nodes too, and a per-node quotient says nothing.
 static bool headroom_coupled(const ykpred_engine* e, int32_t spec, uint32_t pre, uint32_t filt) {
@@ -4574,29 +4447,35 @@ static bool headroom_coupled(const ykpred_engine* e, int32_t spec, uint32_t pre,
 }
 
 // What the ranks of a sharded engine must hold alike beside the ask list — the tune that shapes the chunks, the call's own arguments —
-// as one word for headroom_prepare's agreement: FNV-1a steps over the words (`h` continues a hash).
-static u64 tune_hash(std::initializer_list<u64> words, u64 h = 0x9e3779b97f4a7c15ull) {
-  for (const u64 w : words) h = (h ^ w) * 0x100000001b3ull;
+// as one word for ask_query_prepare's agreement: FNV-1a steps over the words (`h` continues a hash).
+static u64 tune_hash(std::initializer_list<u64> words, u64 h = yktasks::kHashSeed) {
+  for (const u64 w : words) h = (h ^ w) * yktasks::kHashPrime;
   return h;
 }
 
-// What ykpred_headroom and ykpred_headroom_groups share in front of their kernels: the argument checks, the TASKS of the list, the
-// topology histograms, and — on a node-sharded engine — the agreement all-gather.
-extern "C++" {  // (a template: the surrounding block has C linkage)
-struct HeadroomTasks {
-  std::vector<int32_t> task_of, spec, pin;  // ask i of the list → its task; per task the spec and the NodeName pin
-  const int32_t* extra = nullptr;           // [n_asks] or null: a small per-ask value (0..15) that is part of the task key ...
-  std::vector<int32_t> extra_of;            // ... and then its value per task (ykpred_preempt_reach: the limit)
-  bool need_fit = true;                     // NodeResourcesFit must be in both lists (the headroom calls: nothing else bounds the count)
+static_assert(yktasks::kNoNodeName == YKPRED_NO_NODE_NAME && yktasks::kBestLevelShift == ykk::kReachLevelShift &&
+                  yktasks::kBestPodsShift == ykk::kReachPodsShift && yktasks::kBestPodsMax == ykk::kReachPodsMax &&
+                  yktasks::kBestMaxLevel == YKPRED_REACH_MAX_TIERS,
+              "ask_tasks.h reads the keys the kernels pack and the pins of ykpred.h");
+
+// THE DRIVER OF THE PER-ASK QUERIES. What every call that answers a list of asks (ykpred_explain, ykpred_headroom, _groups, _spread,
+// _affinity, ykpred_preempt_reach, _headroom, _victims, _round) does in front of its kernels is ask_query_prepare: the argument checks,
+// the TASKS of the list (ask_tasks.h), the topology histograms, and — on a node-sharded engine — the agreement all-gather. The five calls
+// that reduce one table over every node go on through ask_query_run; the per-node calls (`_pod`) go through pod_query_run.
+extern "C++" {  // (templates: the surrounding block has C linkage)
+struct AskTasks : yktasks::Partition {
+  const int32_t* extra = nullptr;  // [n_asks] or null: a small per-ask value (0..15) that is part of the task key; per task in extra_of
+  bool need_fit = true;            // NodeResourcesFit must be in both lists (the headroom calls: nothing else bounds the count)
   // what a rank names as the cause when ANOTHER rank could not run the call (it knows the status, not the text)
   const char* other_causes = "bad argument, NodeResourcesFit missing from a list, tables not uploaded, an index out of range or stale topology histograms";
 };
+inline int no_more_checks(std::string*) { return YKPRED_OK; }
 // `more_checks` (a callable) runs after the common checks passed and returns a status of the call's own with its text; `more` is a
 // hash of whatever else the ranks of a sharded engine must hold alike. *run == false on return: the caller returns the status at once
 // (an error on some rank, or n_asks == 0).
 template <class MoreChecks>
-static int32_t headroom_prepare(ykpred_engine* e, const std::string& name, int32_t n_asks, const int32_t* asks, bool pointers_ok, uint32_t pre,
-                                uint32_t filt, MoreChecks more_checks, u64 more, HeadroomTasks* tasks, bool* run) {
+static int32_t ask_query_prepare(ykpred_engine* e, const std::string& name, int32_t n_asks, const int32_t* asks, bool pointers_ok, uint32_t pre,
+                                 uint32_t filt, MoreChecks more_checks, u64 more, AskTasks* tasks, bool* run) {
   *run = false;
   const bool sharded = e->comm && e->comm_world > 1;
   int rc = YKPRED_OK;
@@ -4611,30 +4490,7 @@ static int32_t headroom_prepare(ykpred_engine* e, const std::string& name, int32
   if (rc == YKPRED_OK) rc = more_checks(&why);
   if (!sharded && rc != YKPRED_OK) return fail(e, rc, why);
   if (!sharded && n_asks == 0) return YKPRED_OK;
-  // Tasks: the distinct (spec, pin) of the list, keyed as ykpred_explain keys them (a sharded engine cannot key on the pin, a node index
-  // of ITS shard; with by_ask every distinct ask index is a task — the keys every rank derives alike).
-  std::vector<int32_t>&task_of = tasks->task_of, &t_spec = tasks->spec, &t_pin = tasks->pin;
-  const int32_t* extra = tasks->extra;
-  auto build_tasks = [&](bool by_ask) {
-    std::unordered_map<u64, int32_t> index;
-    task_of.assign((size_t)n_asks, 0);
-    t_spec.clear();
-    t_pin.clear();
-    tasks->extra_of.clear();
-    for (int i = 0; i < n_asks; ++i) {
-      const int32_t a = asks[i], sp = e->h_pod_spec[(size_t)a], pin = e->h_pod_pin[(size_t)a];
-      u64 key = ((u64)(uint32_t)sp << 32) | (u64)(uint32_t)pin;
-      if (by_ask || (sharded && pin != YKPRED_NO_NODE_NAME)) key = (1ull << 63) | (u64)(uint32_t)a;
-      if (extra) key |= (u64)(extra[i] & 15) << 59;  // (bits 59..62: free under 2^27 specs, and above an ask index)
-      auto it = index.emplace(key, (int32_t)t_spec.size());
-      if (it.second) {
-        t_spec.push_back(sp);
-        t_pin.push_back(pin);
-        if (extra) tasks->extra_of.push_back(extra[i]);
-      }
-      task_of[(size_t)i] = it.first->second;
-    }
-  };
+  auto build_tasks = [&](bool by_ask) { yktasks::partition(e->h_pod_spec.data(), e->h_pod_pin.data(), n_asks, asks, tasks->extra, sharded, by_ask, tasks); };
   if (rc == YKPRED_OK) build_tasks(false);
   HIPCHK(hipSetDevice(e->cfg.device));
   hipStream_t st = e->own_stream;
@@ -4645,18 +4501,15 @@ static int32_t headroom_prepare(ykpred_engine* e, const std::string& name, int32
     if (rc != YKPRED_OK && !sharded) return rc;
   }
   if (sharded) {
-    // Collective: (status, ask count, list, task partition, the call's own hash) agreed before anybody enters the reduces, as in
-    // ykpred_explain.
+    // Collective: the ranks agree on (status, ask count, list, task partition, the call's own hash) before anybody enters the reduces —
+    // a rank that cannot run, or a different list, is the SAME error on every rank. Partitions that differ (per-shard dictionaries merge
+    // specs differently) are no error: every rank then takes one task per distinct ask.
     struct Agree {
       int32_t rc, n;
-      u64 list, partition, more;
+      uint64_t list, partition, more;
     };
-    Agree mine{rc, n_asks, 0x9e3779b97f4a7c15ull, 0x9e3779b97f4a7c15ull, more};
-    if (rc == YKPRED_OK)
-      for (int i = 0; i < n_asks; ++i) {
-        mine.list = (mine.list ^ (u64)(uint32_t)asks[i]) * 0x100000001b3ull;
-        mine.partition = (mine.partition ^ (u64)(uint32_t)task_of[(size_t)i]) * 0x100000001b3ull;
-      }
+    Agree mine{rc, n_asks, yktasks::kHashSeed, yktasks::kHashSeed, more};
+    if (rc == YKPRED_OK) yktasks::agreement_words(n_asks, asks, tasks->task_of.data(), &mine.list, &mine.partition);
     const int W = e->comm_world;
     HIPCHK(e->d_agree.ensure((size_t)(W + 1) * sizeof(Agree)));
     Agree* d = e->d_agree.as<Agree>();
@@ -4684,10 +4537,136 @@ static int32_t headroom_prepare(ykpred_engine* e, const std::string& name, int32
   *run = true;
   return YKPRED_OK;
 }
+
+// The column of one value per task beside the cells: none; a MAX over the nodes, seeded 0 with the cells; a MIN of packed best keys,
+// seeded with 0x7f bytes (level field 15: no node).
+enum class SideColumn { kNone, kMax, kMin };
+
+// Everything between "prepare returned run" and "the rows are on the host" for the calls that reduce ONE [tasks][B] table of `Cell`s over
+// every node: d_query carved into cells | side column | specs | pins | limits (the table and the side column first: what the reduces and
+// the copy move; limits only for tasks keyed with an extra), the seeds, the uploads, the grid of k_explain, `launch(grid, d_spec, d_pin,
+// d_limit, d_cells, d_side)`, on a sharded engine the SUM of the cells and the MAX or MIN of the side column, one copy and one
+// synchronise. *rows: [tasks][B] cells, then [tasks] side values.
+template <class Cell, class Launch>
+static int32_t ask_query_run(ykpred_engine* e, const AskTasks& tasks, size_t B, SideColumn side, Launch launch, std::vector<Cell>* rows) {
+  static_assert(sizeof(Cell) == 4 || sizeof(Cell) == 8, "int32 or int64 cells");
+  constexpr ncclDataType_t cell_type = sizeof(Cell) == 4 ? ncclInt32 : ncclInt64;
+  const bool sharded = e->comm && e->comm_world > 1, with_limits = tasks.extra != nullptr;
+  hipStream_t st = e->own_stream;
+  const size_t T = tasks.spec.size(), moved = T * (B + (side != SideColumn::kNone));
+  // (a multiple of 8 bytes: under YKPRED_GUARD_PAGES=1 a block is as aligned as its size, and the next call may hold int64 cells)
+  HIPCHK(e->d_query.ensure((moved * sizeof(Cell) + T * (2 + with_limits) * sizeof(int32_t) + 64 + 7) & ~(size_t)7));
+  Cell* d_cells = e->d_query.as<Cell>();
+  Cell* d_side = side != SideColumn::kNone ? d_cells + T * B : nullptr;
+  int32_t* d_spec = (int32_t*)(d_cells + moved);
+  int32_t* d_pin = d_spec + T;
+  int32_t* d_limit = with_limits ? d_pin + T : nullptr;
+  HIPCHK(hipMemsetAsync(d_cells, 0, T * (B + (side == SideColumn::kMax)) * sizeof(Cell), st));
+  if (side == SideColumn::kMin) HIPCHK(hipMemsetAsync(d_side, 0x7f, T * sizeof(Cell), st));
+  if (e->N > 0) {
+    HIPCHK(hipMemcpyAsync(d_spec, tasks.spec.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_pin, tasks.pin.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (with_limits) HIPCHK(hipMemcpyAsync(d_limit, tasks.extra_of.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    const dim3 grid((unsigned)((T + ykk::kExplainTasks - 1) / ykk::kExplainTasks), (unsigned)((e->N + ykk::kBlock - 1) / ykk::kBlock));
+    launch(grid, d_spec, d_pin, d_limit, d_cells, d_side);
+    HIPCHK(hipGetLastError());
+  }
+  if (sharded) {
+    NCCLCHK(rccl()->AllReduce(d_cells, d_cells, T * B, cell_type, ncclSum, e->comm, st));
+    if (side != SideColumn::kNone) NCCLCHK(rccl()->AllReduce(d_side, d_side, T, cell_type, side == SideColumn::kMax ? ncclMax : ncclMin, e->comm, st));
+  }
+  rows->resize(moved);
+  HIPCHK(hipMemcpyAsync(rows->data(), d_cells, moved * sizeof(Cell), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return YKPRED_OK;
+}
+
+// out[i] = the row of ask i's task
+template <class Cell>
+static void scatter_task_rows(const std::vector<Cell>& rows, const AskTasks& tasks, size_t B, Cell* out) {
+  for (size_t i = 0; i < tasks.task_of.size(); ++i) memcpy(out + i * B, rows.data() + (size_t)tasks.task_of[i] * B, B * sizeof(Cell));
+}
+
+// The per-node calls: one 4-byte cell for ONE ask on every node of this table — this shard's nodes on a sharded engine; nothing is
+// exchanged. What a call is:
+struct PodQuery {
+  const char* name;
+  bool need_fit = false;      // NodeResourcesFit must be in both lists (the calls that count copies: nothing else bounds the count)
+  bool coupled_fill = false;  // a coupled ask has no per-node figure: -1 everywhere and nothing runs (so these calls never read the histograms)
+  const char* (*no_table)(const ykpred_engine*) = nullptr;  // the table the call reads: its text when it is missing
+  int ykpred_engine::*tiers = nullptr;                      // the call takes a limit, 0 .. this many tiers
+  bool per_level = false;                                   // limit + 1 cells per node, level-major, instead of one
+};
+// The checks in the order null argument, NodeResourcesFit, tables, the call's table, pod index, limit, so the same error wins when two
+// apply. Then `launch(grid, spec, pin, d_out)`, one copy, one synchronise.
+template <class Out, class Launch>
+static int32_t pod_query_run(ykpred_engine* e, const PodQuery& q, int32_t pod, int32_t limit, uint32_t pre, uint32_t filt, Out* out, Launch launch) {
+  static_assert(sizeof(Out) == 4, "one 4-byte cell");
+  const auto error = [&](int code, const char* what) { return fail(e, code, std::string(q.name) + ": " + what); };
+  if (!e || !out) return error(YKPRED_E_INVALID, "bad argument");
+  if (q.need_fit && !(pre & filt & YKPRED_PLUGIN_NODE_RESOURCES_FIT)) return error(YKPRED_E_INVALID, "NodeResourcesFit must be in both plugin lists (nothing else bounds the count)");
+  if (!e->nodes_set || !e->specs_set || !e->pods_set) return error(YKPRED_E_STATE, "tables not uploaded");
+  if (q.no_table && q.no_table(e)) return error(YKPRED_E_STATE, q.no_table(e));
+  if (pod < 0 || pod >= e->P) return error(YKPRED_E_INVALID, "index out of range");
+  if (q.tiers && (limit < 0 || limit > e->*q.tiers)) return error(YKPRED_E_INVALID, "limit outside 0 .. tiers");
+  if (e->N == 0) return YKPRED_OK;
+  const size_t N = (size_t)e->N, cells = (q.per_level ? (size_t)limit + 1 : 1) * N;
+  const int32_t spec = e->h_pod_spec[(size_t)pod];
+  if (q.coupled_fill && headroom_coupled(e, spec, pre, filt)) {
+    std::fill(out, out + cells, (Out)-1);
+    return YKPRED_OK;
+  }
+  HIPCHK(hipSetDevice(e->cfg.device));
+  hipStream_t st = e->own_stream;
+  // (the histogram preparation of ykpred_query)
+  if (!q.coupled_fill && (pre & filt & (YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD | YKPRED_PLUGIN_INTER_POD_AFFINITY))) TRY(ensure_histograms(e, st));
+  else if (e->spread_dirty) TRY(build_spread_tables(e, st));
+  HIPCHK(e->d_scratch.ensure(cells * sizeof(Out) + 64));
+  launch(dim3((unsigned)((N + ykk::kBlock - 1) / ykk::kBlock)), spec, e->h_pod_pin[(size_t)pod], e->d_scratch.as<Out>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, e->d_scratch.p, cells * sizeof(Out), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return YKPRED_OK;
+}
 }  // extern "C++"
 
+// ykpred_query_pod with ONE 4-byte word per node and one device → host copy: bits 0-7 plugin code, bit 8 fit, bits 9-12 the
+// four reason flags, bits 13.. the insufficient-resource flags (reason >> YKPRED_REASON_RESOURCE_SHIFT).
+int32_t ykpred_query_pod_packed(ykpred_engine_t* e, int32_t pod, uint32_t pre, uint32_t filt, uint32_t* out) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:query_pod");
+  if (e) e->n_queries++;
+  const PodQuery q{"query_pod_packed"};
+  return pod_query_run(e, q, pod, 0, pre, filt, out, [&](dim3 grid, int32_t spec, int32_t pin, uint32_t* d_out) {
+    hipLaunchKernelGGL(ykk::k_query_pod_packed, grid, dim3(ykk::kBlock), 0, e->own_stream, node_table(e), spec_table(e), spec, pin, pre, filt, d_out);
+  });
+}
+
+// Why an ask fits nowhere: the histogram of ykpred_query's verdicts over every node, reduced on the device (k_explain). Reads the
+// tables only — no bitmap, no evaluation state is consulted or changed.
+int32_t ykpred_explain(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, uint32_t pre, uint32_t filt, int32_t* out) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:explain");
+  if (e) e->n_queries++;
+  static_assert(ykk::kExplainBins == YKPRED_EXPLAIN_BINS, "k_explain writes the layout of ykpred.h");
+  constexpr size_t B = YKPRED_EXPLAIN_BINS;
+  if (!e) return YKPRED_E_INVALID;
+  AskTasks tasks;
+  tasks.need_fit = false;
+  tasks.other_causes = "bad argument, tables not uploaded, an index out of range or stale topology histograms";
+  bool run = false;
+  const int32_t rc = ask_query_prepare(e, "explain", n_asks, asks, n_asks <= 0 || (asks && out), pre, filt, no_more_checks, 0, &tasks, &run);
+  if (!run) return rc;
+  std::vector<int32_t> rows;
+  TRY(ask_query_run(e, tasks, B, SideColumn::kNone, [&](dim3 grid, const int32_t* d_spec, const int32_t* d_pin, const int32_t*, int32_t* d_bins, int32_t*) {
+    hipLaunchKernelGGL(ykk::k_explain, grid, dim3(ykk::kBlock), 0, e->own_stream, node_table(e), spec_table(e), (int)tasks.spec.size(), d_spec, d_pin, pre, filt, d_bins);
+  }, &rows));
+  scatter_task_rows(rows, tasks, B, out);
+  return YKPRED_OK;
+}
+
 // How many copies of an ask the cluster still takes: per listed ask the per-node replicas (kernels.hip.h: replicas) reduced over every
-// node on the device (k_headroom). The shape of ykpred_explain — tasks, agreement, one reduce — with an int64 table and a max beside it.
+// node on the device (k_headroom): an int64 table with the MAX of the replicas beside it.
 int32_t ykpred_headroom(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, uint32_t pre, uint32_t filt, int64_t* out) {
   YK_SERIALISE(e);
   Range roctx_range("ykpred:headroom");
@@ -4695,35 +4674,16 @@ int32_t ykpred_headroom(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks,
   static_assert(ykk::kHeadroomCells == YKPRED_HEADROOM_CELLS, "k_headroom writes the layout of ykpred.h");
   constexpr size_t B = YKPRED_HEADROOM_CELLS;
   if (!e) return YKPRED_E_INVALID;
-  HeadroomTasks tasks;
+  AskTasks tasks;
   bool run = false;
-  const int32_t rc = headroom_prepare(e, "headroom", n_asks, asks, n_asks <= 0 || (asks && out), pre, filt, [](std::string*) { return (int)YKPRED_OK; }, 0, &tasks, &run);
+  const int32_t rc = ask_query_prepare(e, "headroom", n_asks, asks, n_asks <= 0 || (asks && out), pre, filt, no_more_checks, 0, &tasks, &run);
   if (!run) return rc;
-  const bool sharded = e->comm && e->comm_world > 1;
-  const std::vector<int32_t>&task_of = tasks.task_of, &t_spec = tasks.spec, &t_pin = tasks.pin;
-  hipStream_t st = e->own_stream;
-  const size_t T = t_spec.size();
-  HIPCHK(e->d_headroom.ensure(T * ((B + 1) * sizeof(int64_t) + 2 * sizeof(int32_t)) + 64));
-  int64_t* d_cells = e->d_headroom.as<int64_t>();  // (the table and the max first: what the reduces and the copy move)
-  int64_t* d_max = d_cells + T * B;
-  int32_t* d_spec = (int32_t*)(d_max + T);
-  int32_t* d_pin = d_spec + T;
-  HIPCHK(hipMemsetAsync(d_cells, 0, T * (B + 1) * sizeof(int64_t), st));
-  if (e->N > 0) {
-    HIPCHK(hipMemcpyAsync(d_spec, t_spec.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_pin, t_pin.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    const dim3 grid((unsigned)((T + ykk::kExplainTasks - 1) / ykk::kExplainTasks), (unsigned)((e->N + ykk::kBlock - 1) / ykk::kBlock));
-    hipLaunchKernelGGL(ykk::k_headroom, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e), (int)T, d_spec, d_pin, pre, filt,
+  const size_t T = tasks.spec.size();
+  std::vector<int64_t> rows;
+  TRY(ask_query_run(e, tasks, B, SideColumn::kMax, [&](dim3 grid, const int32_t* d_spec, const int32_t* d_pin, const int32_t*, int64_t* d_cells, int64_t* d_max) {
+    hipLaunchKernelGGL(ykk::k_headroom, grid, dim3(ykk::kBlock), 0, e->own_stream, node_table(e), spec_table(e), (int)T, d_spec, d_pin, pre, filt,
                        (ykk::i64*)d_cells, (ykk::i64*)d_max);
-    HIPCHK(hipGetLastError());
-  }
-  if (sharded) {
-    NCCLCHK(rccl()->AllReduce(d_cells, d_cells, T * B, ncclInt64, ncclSum, e->comm, st));
-    NCCLCHK(rccl()->AllReduce(d_max, d_max, T, ncclInt64, ncclMax, e->comm, st));
-  }
-  std::vector<int64_t> rows(T * (B + 1));
-  HIPCHK(hipMemcpyAsync(rows.data(), d_cells, T * (B + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  }, &rows));
   // The status per task, decided here: [3] arrives as the number of shards whose spec table does not evaluate the spec.
   for (size_t k = 0; k < T; ++k) {
     int64_t* row = rows.data() + k * B;
@@ -4731,7 +4691,7 @@ int32_t ykpred_headroom(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks,
     if (row[3] != 0) {
       std::fill(row, row + B, (int64_t)0);
       row[3] = 1;
-    } else if (headroom_coupled(e, t_spec[k], pre, filt)) {
+    } else if (headroom_coupled(e, tasks.spec[k], pre, filt)) {
       const int64_t fit = row[1];
       std::fill(row, row + B, (int64_t)0);
       row[0] = row[2] = -1;
@@ -4739,36 +4699,20 @@ int32_t ykpred_headroom(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks,
       row[3] = 2;
     }
   }
-  for (int i = 0; i < n_asks; ++i) memcpy(out + (size_t)i * B, rows.data() + (size_t)task_of[(size_t)i] * B, B * sizeof(int64_t));
+  scatter_task_rows(rows, tasks, B, out);
   return YKPRED_OK;
 }
 
-// replicas of one ask on every node of this table (this shard's nodes on a sharded engine; nothing is exchanged)
+// replicas of one ask on every node of this table
 int32_t ykpred_headroom_pod(ykpred_engine_t* e, int32_t pod, uint32_t pre, uint32_t filt, int32_t* out) {
   YK_SERIALISE(e);
   Range roctx_range("ykpred:headroom_pod");
   if (e) e->n_queries++;
-  if (!e || !out) return fail(e, YKPRED_E_INVALID, "headroom_pod: bad argument");
-  if (!(pre & filt & YKPRED_PLUGIN_NODE_RESOURCES_FIT)) return fail(e, YKPRED_E_INVALID, "headroom_pod: NodeResourcesFit must be in both plugin lists (nothing else bounds the count)");
-  if (!e->nodes_set || !e->specs_set || !e->pods_set) return fail(e, YKPRED_E_STATE, "headroom_pod: tables not uploaded");
-  if (pod < 0 || pod >= e->P) return fail(e, YKPRED_E_INVALID, "headroom_pod: index out of range");
-  if (e->N == 0) return YKPRED_OK;
-  const size_t N = (size_t)e->N;
-  const int32_t spec = e->h_pod_spec[(size_t)pod];
-  if (headroom_coupled(e, spec, pre, filt)) {  // no per-node figure exists for copies that interact across nodes
-    std::fill(out, out + N, (int32_t)-1);
-    return YKPRED_OK;
-  }
-  HIPCHK(hipSetDevice(e->cfg.device));
-  hipStream_t st = e->own_stream;
-  if (e->spread_dirty) TRY(build_spread_tables(e, st));
-  HIPCHK(e->d_scratch.ensure(N * sizeof(int32_t) + 64));
-  hipLaunchKernelGGL(ykk::k_headroom_pod, dim3((unsigned)((N + ykk::kBlock - 1) / ykk::kBlock)), dim3(ykk::kBlock), 0, st, node_table(e),
-                     spec_table(e), spec, e->h_pod_pin[(size_t)pod], pre, filt, e->d_scratch.as<int32_t>());
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, e->d_scratch.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return YKPRED_OK;
+  PodQuery q{"headroom_pod"};
+  q.need_fit = q.coupled_fill = true;
+  return pod_query_run(e, q, pod, 0, pre, filt, out, [&](dim3 grid, int32_t spec, int32_t pin, int32_t* d_out) {
+    hipLaunchKernelGGL(ykk::k_headroom_pod, grid, dim3(ykk::kBlock), 0, e->own_stream, node_table(e), spec_table(e), spec, pin, pre, filt, d_out);
+  });
 }
 
 // The resident reclaim table of ykpred_preempt_reach: three planes beside the node table, shard-local on the node axis. Nothing else reads
@@ -4833,8 +4777,21 @@ static ykk::ReclaimTable reclaim_table(ykpred_engine* e) {
   return rc;
 }
 
-// Which nodes removing lower-priority pods opens: per listed (ask, limit) the level of every node reduced on the device (k_preempt_reach).
-// The shape of ykpred_headroom — tasks, agreement, a SUM reduce — with a MIN of packed best-node keys beside it.
+// What the three preemption queries check beside the common checks — the table they read, one limit per ask inside its tiers — and the
+// hash of it for the agreement. `no_table`: the text when the table is missing, null otherwise.
+static int preempt_limit_checks(const std::string& name, const char* no_table, int tiers, int32_t n_asks, const int32_t* limits, std::string* why) {
+  if (no_table) return *why = name + ": " + no_table, YKPRED_E_STATE;
+  for (int i = 0; i < n_asks; ++i)
+    if (limits[i] < 0 || limits[i] > tiers) return *why = name + ": limit outside 0 .. tiers", YKPRED_E_INVALID;
+  return YKPRED_OK;
+}
+static const char* no_reclaim_table(const ykpred_engine* e) { return e->rc_tiers == 0 ? "no reclaim table (ykpred_set_reclaim)" : nullptr; }
+static const char* no_victim_table(const ykpred_engine* e) {
+  return e->vt_tiers == 0 || e->vt_tiers != e->rc_tiers ? "no victim table (ykpred_set_victims)" : nullptr;
+}
+
+// Which nodes removing lower-priority pods opens: per listed (ask, limit) the level of every node reduced on the device (k_preempt_reach):
+// tasks keyed with the limit, a SUM of the cells, a MIN of packed best-node keys beside it.
 int32_t ykpred_preempt_reach(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, const int32_t* limits, uint32_t pre, uint32_t filt, int64_t* out) {
   YK_SERIALISE(e);
   Range roctx_range("ykpred:preempt_reach");
@@ -4843,100 +4800,47 @@ int32_t ykpred_preempt_reach(ykpred_engine_t* e, int32_t n_asks, const int32_t* 
   constexpr size_t B = YKPRED_REACH_CELLS;
   if (!e) return YKPRED_E_INVALID;
   const bool args_ok = n_asks <= 0 || (asks && limits && out);
-  auto more_checks = [&](std::string* why) -> int {
-    if (e->rc_tiers == 0) return *why = "preempt_reach: no reclaim table (ykpred_set_reclaim)", YKPRED_E_STATE;
-    for (int i = 0; i < n_asks; ++i)
-      if (limits[i] < 0 || limits[i] > e->rc_tiers) return *why = "preempt_reach: limit outside 0 .. tiers", YKPRED_E_INVALID;
-    return YKPRED_OK;
-  };
+  auto more_checks = [&](std::string* why) { return preempt_limit_checks("preempt_reach", no_reclaim_table(e), e->rc_tiers, n_asks, limits, why); };
   u64 more = tune_hash({(u64)(uint32_t)e->rc_tiers});
   if (n_asks > 0 && args_ok)
     for (int i = 0; i < n_asks; ++i) more = tune_hash({(u64)(uint32_t)limits[i]}, more);
-  HeadroomTasks tasks;
+  AskTasks tasks;
   tasks.extra = args_ok && n_asks > 0 ? limits : nullptr;
   tasks.need_fit = false;
   tasks.other_causes = "bad argument, no reclaim table, a limit outside 0 .. tiers, tables not uploaded, an index out of range or stale topology histograms";
   bool run = false;
-  const int32_t rc = headroom_prepare(e, "preempt_reach", n_asks, asks, args_ok, pre, filt, more_checks, more, &tasks, &run);
+  const int32_t rc = ask_query_prepare(e, "preempt_reach", n_asks, asks, args_ok, pre, filt, more_checks, more, &tasks, &run);
   if (!run) return rc;
-  const bool sharded = e->comm && e->comm_world > 1;
-  const std::vector<int32_t>&task_of = tasks.task_of, &t_spec = tasks.spec, &t_pin = tasks.pin, &t_limit = tasks.extra_of;
-  hipStream_t st = e->own_stream;
-  const size_t T = t_spec.size();
-  HIPCHK(e->d_reach.ensure(T * ((B + 1) * sizeof(int64_t) + 3 * sizeof(int32_t)) + 64));
-  int64_t* d_cells = e->d_reach.as<int64_t>();  // (the table and the keys first: what the reduces and the copy move)
-  int64_t* d_best = d_cells + T * B;
-  int32_t* d_spec = (int32_t*)(d_best + T);
-  int32_t* d_pin = d_spec + T;
-  int32_t* d_limit = d_pin + T;
-  HIPCHK(hipMemsetAsync(d_cells, 0, T * B * sizeof(int64_t), st));
-  HIPCHK(hipMemsetAsync(d_best, 0x7f, T * sizeof(int64_t), st));  // (level field 15: no node)
-  if (e->N > 0) {
-    HIPCHK(hipMemcpyAsync(d_spec, t_spec.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_pin, t_pin.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_limit, t_limit.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    const dim3 grid((unsigned)((T + ykk::kExplainTasks - 1) / ykk::kExplainTasks), (unsigned)((e->N + ykk::kBlock - 1) / ykk::kBlock));
-    hipLaunchKernelGGL(ykk::k_preempt_reach, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e), reclaim_table(e), (int)T, d_spec, d_pin,
-                       d_limit, sharded ? e->node_offset : 0, pre, filt, (ykk::i64*)d_cells, (ykk::u64*)d_best);
-    HIPCHK(hipGetLastError());
-  }
-  if (sharded) {
-    NCCLCHK(rccl()->AllReduce(d_cells, d_cells, T * B, ncclInt64, ncclSum, e->comm, st));
-    NCCLCHK(rccl()->AllReduce(d_best, d_best, T, ncclInt64, ncclMin, e->comm, st));
-  }
-  std::vector<int64_t> rows(T * (B + 1));
-  HIPCHK(hipMemcpyAsync(rows.data(), d_cells, T * (B + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  // The status per task, decided here: [10] arrives as the number of shards whose spec table does not evaluate the spec.
-  for (size_t k = 0; k < T; ++k) {
-    int64_t* row = rows.data() + k * B;
-    const u64 key = (u64)rows[T * B + k];
-    const int64_t level = (int64_t)(key >> ykk::kReachLevelShift);
-    if (row[10] != 0) {
-      std::fill(row, row + B, (int64_t)0);
-      row[10] = 1;
-      row[13] = -1;
-    } else if (level >= 1 && level <= YKPRED_REACH_MAX_TIERS) {
-      row[12] = level;
-      row[13] = (int64_t)(key & 0x7fffffffull);
-      row[14] = (int64_t)((key >> ykk::kReachPodsShift) & (u64)ykk::kReachPodsMax);
-    } else {
-      row[13] = -1;
-    }
-    row[11] = t_limit[k];
-  }
-  for (int i = 0; i < n_asks; ++i) memcpy(out + (size_t)i * B, rows.data() + (size_t)task_of[(size_t)i] * B, B * sizeof(int64_t));
+  const size_t T = tasks.spec.size();
+  const int offset = e->comm && e->comm_world > 1 ? e->node_offset : 0;
+  std::vector<int64_t> rows;
+  TRY(ask_query_run(e, tasks, B, SideColumn::kMin, [&](dim3 grid, const int32_t* d_spec, const int32_t* d_pin, const int32_t* d_limit, int64_t* d_cells, int64_t* d_best) {
+    hipLaunchKernelGGL(ykk::k_preempt_reach, grid, dim3(ykk::kBlock), 0, e->own_stream, node_table(e), spec_table(e), reclaim_table(e), (int)T, d_spec, d_pin,
+                       d_limit, offset, pre, filt, (ykk::i64*)d_cells, (ykk::u64*)d_best);
+  }, &rows));
+  // (status [10], limit [11], best level / node / pods [12..14])
+  for (size_t k = 0; k < T; ++k) yktasks::best_key_fixup(rows.data() + k * B, (int)B, 10, (uint64_t)rows[T * B + k], tasks.extra_of[k]);
+  scatter_task_rows(rows, tasks, B, out);
   return YKPRED_OK;
 }
 
-// the level of one ask on every node of this table (this shard's nodes on a sharded engine; nothing is exchanged)
+// the level of one ask on every node of this table
 int32_t ykpred_preempt_reach_pod(ykpred_engine_t* e, int32_t pod, int32_t limit, uint32_t pre, uint32_t filt, int32_t* out) {
   YK_SERIALISE(e);
   Range roctx_range("ykpred:preempt_reach_pod");
   if (e) e->n_queries++;
-  if (!e || !out) return fail(e, YKPRED_E_INVALID, "preempt_reach_pod: bad argument");
-  if (!e->nodes_set || !e->specs_set || !e->pods_set) return fail(e, YKPRED_E_STATE, "preempt_reach_pod: tables not uploaded");
-  if (e->rc_tiers == 0) return fail(e, YKPRED_E_STATE, "preempt_reach_pod: no reclaim table (ykpred_set_reclaim)");
-  if (pod < 0 || pod >= e->P) return fail(e, YKPRED_E_INVALID, "preempt_reach_pod: index out of range");
-  if (limit < 0 || limit > e->rc_tiers) return fail(e, YKPRED_E_INVALID, "preempt_reach_pod: limit outside 0 .. tiers");
-  if (e->N == 0) return YKPRED_OK;
-  HIPCHK(hipSetDevice(e->cfg.device));
-  hipStream_t st = e->own_stream;
-  if ((pre & filt & (YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD | YKPRED_PLUGIN_INTER_POD_AFFINITY))) TRY(ensure_histograms(e, st));
-  else if (e->spread_dirty) TRY(build_spread_tables(e, st));
-  const size_t N = (size_t)e->N;
-  HIPCHK(e->d_scratch.ensure(N * sizeof(int32_t) + 64));
-  hipLaunchKernelGGL(ykk::k_preempt_reach_pod, dim3((unsigned)((N + ykk::kBlock - 1) / ykk::kBlock)), dim3(ykk::kBlock), 0, st, node_table(e),
-                     spec_table(e), reclaim_table(e), e->h_pod_spec[(size_t)pod], e->h_pod_pin[(size_t)pod], limit, pre, filt, e->d_scratch.as<int32_t>());
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, e->d_scratch.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return YKPRED_OK;
+  PodQuery q{"preempt_reach_pod"};
+  q.no_table = no_reclaim_table, q.tiers = &ykpred_engine::rc_tiers;
+  return pod_query_run(e, q, pod, limit, pre, filt, out,
+                       [&](dim3 grid, int32_t spec, int32_t pin, int32_t* d_out) {
+                         hipLaunchKernelGGL(ykk::k_preempt_reach_pod, grid, dim3(ykk::kBlock), 0, e->own_stream, node_table(e), spec_table(e), reclaim_table(e),
+                                            spec, pin, limit, pre, filt, d_out);
+                       });
 }
 
 // Copies of an ask per preemption level: ykpred_headroom's replicas on the node states of ykpred_preempt_reach, reduced per level on the
-// device (k_preempt_headroom). The driver of ykpred_preempt_reach — tasks keyed with the limit, the agreement, ONE SUM reduce of the
-// per-level deltas — and then the finish of preempt_headroom_finish.h per listed ask, on every rank alike: the want is read only there.
+// device (k_preempt_headroom): tasks keyed with the limit, ONE SUM reduce of the per-level deltas — and then the finish of
+// preempt_headroom_finish.h per listed ask, on every rank alike: the want is read only there.
 int32_t ykpred_preempt_headroom(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, const int32_t* limits, const int64_t* wants, uint32_t pre,
                                 uint32_t filt, int64_t* out) {
   YK_SERIALISE(e);
@@ -4949,9 +4853,7 @@ int32_t ykpred_preempt_headroom(ykpred_engine_t* e, int32_t n_asks, const int32_
   if (!e) return YKPRED_E_INVALID;
   const bool args_ok = n_asks <= 0 || (asks && limits && out);
   auto more_checks = [&](std::string* why) -> int {
-    if (e->rc_tiers == 0) return *why = "preempt_headroom: no reclaim table (ykpred_set_reclaim)", YKPRED_E_STATE;
-    for (int i = 0; i < n_asks; ++i)
-      if (limits[i] < 0 || limits[i] > e->rc_tiers) return *why = "preempt_headroom: limit outside 0 .. tiers", YKPRED_E_INVALID;
+    TRY(preempt_limit_checks("preempt_headroom", no_reclaim_table(e), e->rc_tiers, n_asks, limits, why));
     if (wants)
       for (int i = 0; i < n_asks; ++i)
         if (wants[i] < 1) return *why = "preempt_headroom: want below 1", YKPRED_E_INVALID;
@@ -4960,71 +4862,38 @@ int32_t ykpred_preempt_headroom(ykpred_engine_t* e, int32_t n_asks, const int32_
   u64 more = tune_hash({(u64)(uint32_t)e->rc_tiers});
   if (n_asks > 0 && args_ok)
     for (int i = 0; i < n_asks; ++i) more = tune_hash({(u64)(uint32_t)limits[i], (u64)(wants ? wants[i] : 1)}, more);
-  HeadroomTasks tasks;
+  AskTasks tasks;
   tasks.extra = args_ok && n_asks > 0 ? limits : nullptr;
   tasks.other_causes = "bad argument, NodeResourcesFit missing from a list, no reclaim table, a limit outside 0 .. tiers, a want below 1, tables not uploaded, an index out of range or stale topology histograms";
   bool run = false;
-  const int32_t rc = headroom_prepare(e, "preempt_headroom", n_asks, asks, args_ok, pre, filt, more_checks, more, &tasks, &run);
+  const int32_t rc = ask_query_prepare(e, "preempt_headroom", n_asks, asks, args_ok, pre, filt, more_checks, more, &tasks, &run);
   if (!run) return rc;
-  const bool sharded = e->comm && e->comm_world > 1;
-  const std::vector<int32_t>&task_of = tasks.task_of, &t_spec = tasks.spec, &t_pin = tasks.pin, &t_limit = tasks.extra_of;
-  hipStream_t st = e->own_stream;
-  const size_t T = t_spec.size();
-  HIPCHK(e->d_reach.ensure(T * (B * sizeof(int64_t) + 3 * sizeof(int32_t)) + 64));
-  int64_t* d_cells = e->d_reach.as<int64_t>();
-  int32_t* d_spec = (int32_t*)(d_cells + T * B);
-  int32_t* d_pin = d_spec + T;
-  int32_t* d_limit = d_pin + T;
-  HIPCHK(hipMemsetAsync(d_cells, 0, T * B * sizeof(int64_t), st));
-  if (e->N > 0) {
-    HIPCHK(hipMemcpyAsync(d_spec, t_spec.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_pin, t_pin.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_limit, t_limit.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    const dim3 grid((unsigned)((T + ykk::kExplainTasks - 1) / ykk::kExplainTasks), (unsigned)((e->N + ykk::kBlock - 1) / ykk::kBlock));
-    hipLaunchKernelGGL(ykk::k_preempt_headroom, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e), reclaim_table(e), (int)T, d_spec,
-                       d_pin, d_limit, pre, filt, (ykk::i64*)d_cells);
-    HIPCHK(hipGetLastError());
-  }
-  if (sharded) NCCLCHK(rccl()->AllReduce(d_cells, d_cells, T * B, ncclInt64, ncclSum, e->comm, st));
-  std::vector<int64_t> rows(T * B);
-  HIPCHK(hipMemcpyAsync(rows.data(), d_cells, T * B * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  std::vector<int64_t> rows;
+  TRY(ask_query_run(e, tasks, B, SideColumn::kNone, [&](dim3 grid, const int32_t* d_spec, const int32_t* d_pin, const int32_t* d_limit, int64_t* d_cells, int64_t*) {
+    hipLaunchKernelGGL(ykk::k_preempt_headroom, grid, dim3(ykk::kBlock), 0, e->own_stream, node_table(e), spec_table(e), reclaim_table(e), (int)tasks.spec.size(),
+                       d_spec, d_pin, d_limit, pre, filt, (ykk::i64*)d_cells);
+  }, &rows));
   // ([27] arrives as the number of shards whose spec table does not evaluate the spec; the coupled rule is ykpred_headroom's)
   for (int i = 0; i < n_asks; ++i) {
-    const size_t k = (size_t)task_of[(size_t)i];
-    ykfinish::preempt_headroom_finish(rows.data() + k * B, t_limit[k], wants ? wants[i] : 1, headroom_coupled(e, t_spec[k], pre, filt), out + (size_t)i * B);
+    const size_t k = (size_t)tasks.task_of[(size_t)i];
+    ykfinish::preempt_headroom_finish(rows.data() + k * B, tasks.extra_of[k], wants ? wants[i] : 1, headroom_coupled(e, tasks.spec[k], pre, filt), out + (size_t)i * B);
   }
   return YKPRED_OK;
 }
 
-// rep_L of one ask on every node of this table, L = 0 .. limit (this shard's nodes on a sharded engine; nothing is exchanged)
+// rep_L of one ask on every node of this table, L = 0 .. limit
 int32_t ykpred_preempt_headroom_pod(ykpred_engine_t* e, int32_t pod, int32_t limit, uint32_t pre, uint32_t filt, int32_t* out) {
   YK_SERIALISE(e);
   Range roctx_range("ykpred:preempt_headroom_pod");
   if (e) e->n_queries++;
-  if (!e || !out) return fail(e, YKPRED_E_INVALID, "preempt_headroom_pod: bad argument");
-  if (!(pre & filt & YKPRED_PLUGIN_NODE_RESOURCES_FIT)) return fail(e, YKPRED_E_INVALID, "preempt_headroom_pod: NodeResourcesFit must be in both plugin lists (nothing else bounds the count)");
-  if (!e->nodes_set || !e->specs_set || !e->pods_set) return fail(e, YKPRED_E_STATE, "preempt_headroom_pod: tables not uploaded");
-  if (e->rc_tiers == 0) return fail(e, YKPRED_E_STATE, "preempt_headroom_pod: no reclaim table (ykpred_set_reclaim)");
-  if (pod < 0 || pod >= e->P) return fail(e, YKPRED_E_INVALID, "preempt_headroom_pod: index out of range");
-  if (limit < 0 || limit > e->rc_tiers) return fail(e, YKPRED_E_INVALID, "preempt_headroom_pod: limit outside 0 .. tiers");
-  if (e->N == 0) return YKPRED_OK;
-  const size_t N = (size_t)e->N, cells = (size_t)(limit + 1) * N;
-  const int32_t spec = e->h_pod_spec[(size_t)pod];
-  if (headroom_coupled(e, spec, pre, filt)) {  // no per-node figure exists for copies that interact across nodes
-    std::fill(out, out + cells, (int32_t)-1);
-    return YKPRED_OK;
-  }
-  HIPCHK(hipSetDevice(e->cfg.device));
-  hipStream_t st = e->own_stream;
-  if (e->spread_dirty) TRY(build_spread_tables(e, st));
-  HIPCHK(e->d_scratch.ensure(cells * sizeof(int32_t) + 64));
-  hipLaunchKernelGGL(ykk::k_preempt_headroom_pod, dim3((unsigned)((N + ykk::kBlock - 1) / ykk::kBlock)), dim3(ykk::kBlock), 0, st, node_table(e),
-                     spec_table(e), reclaim_table(e), spec, e->h_pod_pin[(size_t)pod], limit, pre, filt, e->d_scratch.as<int32_t>());
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, e->d_scratch.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return YKPRED_OK;
+  PodQuery q{"preempt_headroom_pod"};
+  q.need_fit = q.coupled_fill = q.per_level = true;
+  q.no_table = no_reclaim_table, q.tiers = &ykpred_engine::rc_tiers;
+  return pod_query_run(e, q, pod, limit, pre, filt, out,
+                       [&](dim3 grid, int32_t spec, int32_t pin, int32_t* d_out) {
+                         hipLaunchKernelGGL(ykk::k_preempt_headroom_pod, grid, dim3(ykk::kBlock), 0, e->own_stream, node_table(e), spec_table(e),
+                                            reclaim_table(e), spec, pin, limit, pre, filt, d_out);
+                       });
 }
 
 // The resident victim table of ykpred_preempt_victims: one row per eligible pod, one segment per node, beside the reclaim table and
@@ -5120,7 +4989,7 @@ static ykk::VictimTable victim_table(ykpred_engine* e) {
 }
 
 // The shortest victim prefix on every node: per listed (ask, limit) the need of every node reduced on the device (k_preempt_victims).
-// ykpred_preempt_reach's shape throughout — tasks, agreement, a SUM reduce of the cells, a MIN of the packed best keys.
+// ykpred_preempt_reach's call throughout, on the victim table: a SUM of the cells, a MIN of the packed best keys.
 int32_t ykpred_preempt_victims(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, const int32_t* limits, uint32_t pre, uint32_t filt, int64_t* out) {
   YK_SERIALISE(e);
   Range roctx_range("ykpred:preempt_victims");
@@ -5129,100 +4998,47 @@ int32_t ykpred_preempt_victims(ykpred_engine_t* e, int32_t n_asks, const int32_t
   constexpr size_t B = YKPRED_VICTIM_CELLS;
   if (!e) return YKPRED_E_INVALID;
   const bool args_ok = n_asks <= 0 || (asks && limits && out);
-  auto more_checks = [&](std::string* why) -> int {
-    if (e->vt_tiers == 0 || e->vt_tiers != e->rc_tiers) return *why = "preempt_victims: no victim table (ykpred_set_victims)", YKPRED_E_STATE;
-    for (int i = 0; i < n_asks; ++i)
-      if (limits[i] < 0 || limits[i] > e->vt_tiers) return *why = "preempt_victims: limit outside 0 .. tiers", YKPRED_E_INVALID;
-    return YKPRED_OK;
-  };
+  auto more_checks = [&](std::string* why) { return preempt_limit_checks("preempt_victims", no_victim_table(e), e->vt_tiers, n_asks, limits, why); };
   u64 more = tune_hash({(u64)(uint32_t)e->vt_tiers, 0x76696374ull});
   if (n_asks > 0 && args_ok)
     for (int i = 0; i < n_asks; ++i) more = tune_hash({(u64)(uint32_t)limits[i]}, more);
-  HeadroomTasks tasks;
+  AskTasks tasks;
   tasks.extra = args_ok && n_asks > 0 ? limits : nullptr;
   tasks.need_fit = false;
   tasks.other_causes = "bad argument, no victim table, a limit outside 0 .. tiers, tables not uploaded, an index out of range or stale topology histograms";
   bool run = false;
-  const int32_t rc = headroom_prepare(e, "preempt_victims", n_asks, asks, args_ok, pre, filt, more_checks, more, &tasks, &run);
+  const int32_t rc = ask_query_prepare(e, "preempt_victims", n_asks, asks, args_ok, pre, filt, more_checks, more, &tasks, &run);
   if (!run) return rc;
-  const bool sharded = e->comm && e->comm_world > 1;
-  const std::vector<int32_t>&task_of = tasks.task_of, &t_spec = tasks.spec, &t_pin = tasks.pin, &t_limit = tasks.extra_of;
-  hipStream_t st = e->own_stream;
-  const size_t T = t_spec.size();
-  HIPCHK(e->d_victims.ensure(T * ((B + 1) * sizeof(int64_t) + 3 * sizeof(int32_t)) + 64));
-  int64_t* d_cells = e->d_victims.as<int64_t>();  // (the table and the keys first: what the reduces and the copy move)
-  int64_t* d_best = d_cells + T * B;
-  int32_t* d_spec = (int32_t*)(d_best + T);
-  int32_t* d_pin = d_spec + T;
-  int32_t* d_limit = d_pin + T;
-  HIPCHK(hipMemsetAsync(d_cells, 0, T * B * sizeof(int64_t), st));
-  HIPCHK(hipMemsetAsync(d_best, 0x7f, T * sizeof(int64_t), st));  // (level field 15: no node)
-  if (e->N > 0) {
-    HIPCHK(hipMemcpyAsync(d_spec, t_spec.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_pin, t_pin.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_limit, t_limit.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    const dim3 grid((unsigned)((T + ykk::kExplainTasks - 1) / ykk::kExplainTasks), (unsigned)((e->N + ykk::kBlock - 1) / ykk::kBlock));
-    hipLaunchKernelGGL(ykk::k_preempt_victims, grid, dim3(ykk::kBlock), 0, st, node_table(e), spec_table(e), victim_table(e), (int)T, d_spec, d_pin,
-                       d_limit, sharded ? e->node_offset : 0, pre, filt, (ykk::i64*)d_cells, (ykk::u64*)d_best);
-    HIPCHK(hipGetLastError());
-  }
-  if (sharded) {
-    NCCLCHK(rccl()->AllReduce(d_cells, d_cells, T * B, ncclInt64, ncclSum, e->comm, st));
-    NCCLCHK(rccl()->AllReduce(d_best, d_best, T, ncclInt64, ncclMin, e->comm, st));
-  }
-  std::vector<int64_t> rows(T * (B + 1));
-  HIPCHK(hipMemcpyAsync(rows.data(), d_cells, T * (B + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  // The status per task, decided here: [3] arrives as the number of shards whose spec table does not evaluate the spec.
-  for (size_t k = 0; k < T; ++k) {
-    int64_t* row = rows.data() + k * B;
-    const u64 key = (u64)rows[T * B + k];
-    const int64_t level = (int64_t)(key >> ykk::kReachLevelShift);
-    if (row[3] != 0) {
-      std::fill(row, row + B, (int64_t)0);
-      row[3] = 1;
-      row[6] = -1;
-    } else if (level >= 1 && level <= YKPRED_REACH_MAX_TIERS) {
-      row[5] = level;
-      row[6] = (int64_t)(key & 0x7fffffffull);
-      row[7] = (int64_t)((key >> ykk::kReachPodsShift) & (u64)ykk::kReachPodsMax);
-    } else {
-      row[6] = -1;
-    }
-    row[4] = t_limit[k];
-  }
-  for (int i = 0; i < n_asks; ++i) memcpy(out + (size_t)i * B, rows.data() + (size_t)task_of[(size_t)i] * B, B * sizeof(int64_t));
+  const size_t T = tasks.spec.size();
+  const int offset = e->comm && e->comm_world > 1 ? e->node_offset : 0;
+  std::vector<int64_t> rows;
+  TRY(ask_query_run(e, tasks, B, SideColumn::kMin, [&](dim3 grid, const int32_t* d_spec, const int32_t* d_pin, const int32_t* d_limit, int64_t* d_cells, int64_t* d_best) {
+    hipLaunchKernelGGL(ykk::k_preempt_victims, grid, dim3(ykk::kBlock), 0, e->own_stream, node_table(e), spec_table(e), victim_table(e), (int)T, d_spec, d_pin,
+                       d_limit, offset, pre, filt, (ykk::i64*)d_cells, (ykk::u64*)d_best);
+  }, &rows));
+  // (status [3], limit [4], best level / node / need [5..7])
+  for (size_t k = 0; k < T; ++k) yktasks::best_key_fixup(rows.data() + k * B, (int)B, 3, (uint64_t)rows[T * B + k], tasks.extra_of[k]);
+  scatter_task_rows(rows, tasks, B, out);
   return YKPRED_OK;
 }
 
-// need of one ask on every node of this table (this shard's nodes on a sharded engine; nothing is exchanged)
+// need of one ask on every node of this table
 int32_t ykpred_preempt_victims_pod(ykpred_engine_t* e, int32_t pod, int32_t limit, uint32_t pre, uint32_t filt, int32_t* out) {
   YK_SERIALISE(e);
   Range roctx_range("ykpred:preempt_victims_pod");
   if (e) e->n_queries++;
-  if (!e || !out) return fail(e, YKPRED_E_INVALID, "preempt_victims_pod: bad argument");
-  if (!e->nodes_set || !e->specs_set || !e->pods_set) return fail(e, YKPRED_E_STATE, "preempt_victims_pod: tables not uploaded");
-  if (e->vt_tiers == 0 || e->vt_tiers != e->rc_tiers) return fail(e, YKPRED_E_STATE, "preempt_victims_pod: no victim table (ykpred_set_victims)");
-  if (pod < 0 || pod >= e->P) return fail(e, YKPRED_E_INVALID, "preempt_victims_pod: index out of range");
-  if (limit < 0 || limit > e->vt_tiers) return fail(e, YKPRED_E_INVALID, "preempt_victims_pod: limit outside 0 .. tiers");
-  if (e->N == 0) return YKPRED_OK;
-  HIPCHK(hipSetDevice(e->cfg.device));
-  hipStream_t st = e->own_stream;
-  if ((pre & filt & (YKPRED_PLUGIN_POD_TOPOLOGY_SPREAD | YKPRED_PLUGIN_INTER_POD_AFFINITY))) TRY(ensure_histograms(e, st));
-  else if (e->spread_dirty) TRY(build_spread_tables(e, st));
-  const size_t N = (size_t)e->N;
-  HIPCHK(e->d_scratch.ensure(N * sizeof(int32_t) + 64));
-  hipLaunchKernelGGL(ykk::k_preempt_victims_pod, dim3((unsigned)((N + ykk::kBlock - 1) / ykk::kBlock)), dim3(ykk::kBlock), 0, st, node_table(e),
-                     spec_table(e), victim_table(e), e->h_pod_spec[(size_t)pod], e->h_pod_pin[(size_t)pod], limit, pre, filt, e->d_scratch.as<int32_t>());
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, e->d_scratch.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return YKPRED_OK;
+  PodQuery q{"preempt_victims_pod"};
+  q.no_table = no_victim_table, q.tiers = &ykpred_engine::vt_tiers;
+  return pod_query_run(e, q, pod, limit, pre, filt, out,
+                       [&](dim3 grid, int32_t spec, int32_t pin, int32_t* d_out) {
+                         hipLaunchKernelGGL(ykk::k_preempt_victims_pod, grid, dim3(ykk::kBlock), 0, e->own_stream, node_table(e), spec_table(e), victim_table(e),
+                                            spec, pin, limit, pre, filt, d_out);
+                       });
 }
 
 // Victim plans for a list of asks, conflict-resolved: per ask one k_preempt_round_step over every node and one
 // k_preempt_round_apply wave, queued back to back on the engine's stream with the round's zeroed state columns between them; one
-// readback at the end. headroom_prepare does the checks and the agreement; its tasks are not used (every occurrence is its own turn).
+// readback at the end. ask_query_prepare does the checks and the agreement; its tasks are not used (every occurrence is its own turn).
 int32_t ykpred_preempt_round(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, const int32_t* limits, uint32_t pre, uint32_t filt,
                              int64_t* out_cells, int64_t* out_summary) {
   YK_SERIALISE(e);
@@ -5243,11 +5059,11 @@ int32_t ykpred_preempt_round(ykpred_engine_t* e, int32_t n_asks, const int32_t* 
   u64 more = tune_hash({(u64)(uint32_t)e->vt_tiers, 0x726f756eull, (u64)pre, (u64)filt});
   if (n_asks > 0 && args_ok)
     for (int i = 0; i < n_asks; ++i) more = tune_hash({(u64)(uint32_t)limits[i]}, more);
-  HeadroomTasks tasks;
+  AskTasks tasks;
   tasks.need_fit = false;
   tasks.other_causes = "bad argument, no victim table, a limit outside 0 .. tiers, tables not uploaded, an index out of range or stale topology histograms";
   bool run = false;
-  const int32_t rc = headroom_prepare(e, "preempt_round", n_asks, asks, args_ok, pre, filt, more_checks, more, &tasks, &run);
+  const int32_t rc = ask_query_prepare(e, "preempt_round", n_asks, asks, args_ok, pre, filt, more_checks, more, &tasks, &run);
   if (out_summary && (run || rc == YKPRED_OK)) std::fill(out_summary, out_summary + B, (int64_t)0);
   if (!run) return rc;
   const bool sharded = e->comm && e->comm_world > 1;
@@ -5334,9 +5150,9 @@ int32_t ykpred_headroom_groups(ykpred_engine_t* e, int32_t n_asks, const int32_t
   u64 more = tune_hash({(u64)(uint32_t)G, (u64)(uint32_t)e->group_scratch_mb, (u64)(uint32_t)e->group_chunk_tasks});
   if (n_asks > 0 && asks && out_summary)
     for (int i = 0; i < n_asks; ++i) more = tune_hash({(u64)(want ? want[i] : 1)}, more);
-  HeadroomTasks tasks;
+  AskTasks tasks;
   bool run = false;
-  const int32_t rc = headroom_prepare(e, "headroom_groups", n_asks, asks, n_asks <= 0 || (asks && out_summary), pre, filt, more_checks, more, &tasks, &run);
+  const int32_t rc = ask_query_prepare(e, "headroom_groups", n_asks, asks, n_asks <= 0 || (asks && out_summary), pre, filt, more_checks, more, &tasks, &run);
   if (!run) return rc;
   const bool sharded = e->comm && e->comm_world > 1;
   hipStream_t st = e->own_stream;
@@ -5486,9 +5302,9 @@ static int32_t headroom_domains_run(V& v, int32_t n_asks, const int32_t* asks, b
   constexpr size_t B = V::kCells, X = V::kExtra, RC = ykk::kSpreadRowCells;
   ykpred_engine* e = v.e;
   const u64 more = v.hash(tune_hash({(u64)(uint32_t)e->group_scratch_mb, (u64)(uint32_t)e->group_chunk_tasks, (u64)(uint32_t)e->group_lds}));
-  HeadroomTasks tasks;
+  AskTasks tasks;
   bool run = false;
-  const int32_t rc = headroom_prepare(e, v.name, n_asks, asks, pointers_ok, v.pre, v.filt, [&](std::string* why) { return v.checks(why); }, more, &tasks, &run);
+  const int32_t rc = ask_query_prepare(e, v.name, n_asks, asks, pointers_ok, v.pre, v.filt, [&](std::string* why) { return v.checks(why); }, more, &tasks, &run);
   if (!run) return rc;
   const bool sharded = e->comm && e->comm_world > 1;
   hipStream_t st = e->own_stream;
