@@ -432,6 +432,35 @@ int32_t ykhost_preempt_gang_by_key(ykhost_t* h, const char* allocation_key, int3
                                    int64_t* needed2 /* [2] or NULL */);
 int32_t ykhost_victim_range(ykhost_t* h, int32_t node, int32_t from, int32_t count, char* uids_buf, int64_t len, int32_t* got, int64_t* needed);
 
+/* PREEMPTION ROUND WITH LIVE TOPOLOGY HISTOGRAMS (ykpred.h: ykpred_preempt_round_live) — ykhost_preempt_round for lists that hold asks with
+ * a hard topology spread, required pod affinity or anti-affinity: no ask is settled as coupled (outcome 4 never occurs), every ask takes
+ * its turn against the histograms as the earlier placements AND the earlier victims left them. What the caller's loop of
+ * ykhost_preempt_victims_by_key, ykhost_remove_pod per victim and ykhost_assume_pod per ask answers for such asks, in one call that
+ * changes nothing in the mirror or on the device.
+ *   ykhost_preempt_round_live          as ykhost_preempt_round; before the engine call the specs' effects and the VICTIM-EFFECTS PLANE
+ *                                      are brought up to date. The mirror derives no plane before the first live call (or
+ *                                      ykhost_victim_effects); from then on victims_refresh patches it with the segments of changed nodes
+ *                                      and derives it anew when the selector classes move or a class gains its first contributing
+ *                                      victim. out_counts [counts_len] / out_minima [minima_len] (each may be NULL) receive the
+ *                                      round-local histograms after the last turn, as far as they fit; hist_needed2 (may be NULL) =
+ *                                      { histogram cells, constraints }. out_summary[7] = (turn, constraint) pairs that moved a cell.
+ *   ykhost_preempt_round_live_by_keys  ykhost_preempt_round_by_keys over the live round, one crossing.
+ *   ykhost_preempt_gang_live_by_key    ykhost_preempt_gang_by_key over the live round: where a gang with a zone spread or a "one per
+ *                                      host" rule goes and at whose cost.
+ *   ykhost_victim_effects              the plane as the mirror keeps it, copied out: dims = { KS, KA, P, planes derived, segments
+ *                                      patched }; class_col [KS] (-1: no column), cum [KA][P] prefix sums within the segment (either
+ *                                      NULL: only the dims come back). Works on a mirror-only handle. */
+int32_t ykhost_preempt_round_live(ykhost_t* h, int32_t n, const int32_t* asks /* NULL = asks 0..n-1 */, int64_t* out_cells /* [n][8] */,
+                                  int64_t* out_summary /* [8] */, int32_t* out_counts, int64_t counts_len, int32_t* out_minima, int64_t minima_len,
+                                  int64_t* hist_needed2 /* [2] or NULL */);
+int32_t ykhost_preempt_round_live_by_keys(ykhost_t* h, int32_t n, const char* const* allocation_keys, int64_t* out_cells /* [n][8] */,
+                                          int64_t* out_summary /* [8] */, char* node_names, int64_t names_len, char* victim_uids, int64_t uids_len,
+                                          int64_t* needed2 /* [2] or NULL */);
+int32_t ykhost_preempt_gang_live_by_key(ykhost_t* h, const char* allocation_key, int32_t want, int64_t* out_cells /* [want][8] */,
+                                        int64_t* out_summary /* [8] */, char* node_names, int64_t names_len, char* victim_uids, int64_t uids_len,
+                                        int64_t* needed2 /* [2] or NULL */);
+int32_t ykhost_victim_effects(ykhost_t* h, int32_t* dims /* [5] */, int32_t* class_col, int32_t* cum);
+
 /* Engine calls that came back YKPRED_E_DEVICE / YKPRED_E_NOMEM so far (failed allocation, lost device). Each one marks the whole
  * device state stale: the failing call returns its error (Predicates() < 0: the Go manager routes the ask to the CPU predicate
  * manager — SURVEY.md §5, "must degrade, never fail scheduling"), the mirror stays intact, and the next ykhost_sync /

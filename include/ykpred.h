@@ -38,7 +38,9 @@
 extern "C" {
 #endif
 
-/* (ykpred_preempt_round + YKPRED_PREEMPT_ROUND_CELLS arrived WITHIN version 4 too: dlsym("ykpred_preempt_round"))
+/* (ykpred_preempt_round_live + ykpred_histogram_dims + ykpred_set_victim_effects + ykpred_update_victim_effects_node + ykpred_victim_effects_t arrived WITHIN
+ *    version 4 too: dlsym("ykpred_preempt_round_live"))
+ * (ykpred_preempt_round + YKPRED_PREEMPT_ROUND_CELLS arrived WITHIN version 4 too: dlsym("ykpred_preempt_round"))
  * (ykpred_preempt_victims + ykpred_preempt_victims_pod + ykpred_set_victims + ykpred_update_victims_node + YKPRED_VICTIM_CELLS arrived
  *    WITHIN version 4 too: dlsym("ykpred_preempt_victims"))
  * (ykpred_preempt_headroom + ykpred_preempt_headroom_pod + YKPRED_PREEMPT_HEADROOM_CELLS arrived WITHIN version 4 too:
@@ -882,6 +884,69 @@ int32_t ykpred_preempt_victims_pod(ykpred_engine_t* e, int32_t pod_index, int32_
 int32_t ykpred_preempt_round(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks /* host, ask indices, list order, repeats = copies */,
                              const int32_t* limits /* host, [n_asks], 0..T */, uint32_t prefilter_plugins, uint32_t filter_plugins,
                              int64_t* out_cells /* host, [n_asks][YKPRED_PREEMPT_ROUND_CELLS] */, int64_t* out_summary /* host, [8] */);
+
+/* PREEMPTION ROUND WITH LIVE TOPOLOGY HISTOGRAMS: ykpred_preempt_round for lists that hold COUPLED asks — asks whose
+ * verdicts read the PodTopologySpread / InterPodAffinity histograms. ykpred_preempt_round, its kernels and its cells are unchanged.
+ *
+ * The VICTIM-EFFECTS PLANE is resident beside the victim table, row for row: what the victims of every prefix contributed to the
+ * selector classes of the node table (ykpred_nodes_t.selector_count). A victim's contribution to class s is what the host's encoder adds
+ * to selector_count[s] for that pod (a terminating pod adds nothing to a PodTopologySpread class); the contributions of ALL pods of a
+ * node sum to its selector_count column. */
+typedef struct ykpred_victim_effects {
+  int32_t classes;          /* KS of the node table */
+  int32_t columns;          /* KA <= KS: the classes some eligible pod contributes to */
+  int64_t rows;             /* P of the resident victim table */
+  const int32_t* class_col; /* [KS] the column of class s, or -1: no eligible pod contributes to it */
+  const int32_t* cum;       /* [KA][P] PREFIX sums within the segment, like ykpred_victims_t.cum: row p = victims 0..p of its node */
+} ykpred_victim_effects_t;
+/* Uploads the plane for the resident victim table (YKPRED_E_STATE without one; YKPRED_E_INVALID when rows or classes differ from the
+ * victim table's P / the node table's KS, or class_col leaves -1..KA-1). NULL drops it; ykpred_set_victims drops it as well.
+ * THE CALLER'S DUTY: the engine checks the plane's shape (rows, KS) and that no segment was patched without its rows; it cannot see what
+ * a selector class MEANS. A caller that uploads node or spec tables encoded under another selector-class dictionary must upload the
+ * victim table and this plane again (the host library does: it ties the plane to a digest of its topology dictionaries). */
+int32_t ykpred_set_victim_effects(ykpred_engine_t* e, const ykpred_victim_effects_t* fx);
+/* Rewrites ONE node's rows: cum [KA][count], count <= seg_cap[node_index] (YKPRED_E_INVALID otherwise, nothing written). A
+ * ykpred_update_victims_node marks the node's plane rows as stale until this call follows it. */
+int32_t ykpred_update_victim_effects_node(ykpred_engine_t* e, int32_t node_index, int32_t count, const int32_t* cum);
+
+/* ROUND STATE: ykpred_preempt_round's, plus a round-local copy of the histogram counts (layout.spread_counts) and of the per-constraint
+ *   minima (what the Filters read as the global minimum / the domains with a match: [G], constraint order), with the running minimum over the present domains and the number of domains that sit there. The copy is
+ *   taken from the engine's prepared histograms at the start of EVERY call; nothing persists; the engine's histograms and every table are
+ *   unchanged after the call.
+ * TURN: need' and the choice are ykpred_preempt_round's, evaluated against the round-local histograms as they stand at the START of the
+ *   turn: within a turn they are frozen, the ask's own victims included (PreemptionPredicates' rule, §4.16-4.18) — a topology failure is
+ *   still a failure no removal opens.
+ * APPLY: ykpred_preempt_round's, and then for the chosen node n and EVERY constraint g of EVERY signature (selector class ks, key kd):
+ *   delta_g = (what one pod of the ask's spec adds to class ks: ykpred_set_spec_effects) - (what the victims order(n)[from .. from+extra)
+ *   contributed to ks: two cells of the plane), applied in domain domain_id[kd][n] — only where a pod on n counts for g (the node carries
+ *   the key with an id inside the row; for a PodTopologySpread constraint the node carries every key of the signature's spread
+ *   constraints and passes the inclusion policies the constraint honors: ykpred_allocate_round's assume test). The cell moves by delta_g,
+ *   which can have either sign; a spread constraint's minimum, domains-at-minimum and minimum after the minDomains rule are recomputed; an
+ *   InterPodAffinity row's minimum cell (domains with a match) moves by one when the cell crosses zero, in either direction. EVERY placed
+ *   ask applies its effects, coupled or not: an uncoupled pod can match a later ask's selector.
+ * OUTCOMES 0-3 as ykpred_preempt_round; outcome 4 never occurs. Cells [0..7] keep their meaning.
+ * out_summary[7] = the (turn, constraint) pairs with an applied delta_g != 0; [0..6] as ykpred_preempt_round.
+ * out_counts / out_minima (each may be NULL): the round-local histograms after the last turn, in the layout's cell order.
+ * IDENTITIES: (1) with non-increasing limits the live round equals, step by step, the host loop "need per node via
+ *   ykpred_preempt_victims_pod -> the victims removed from the node -> the ask assumed on it" on fresh tables, coupled asks included;
+ *   (2) a list with no coupled ask, on specs and victims that contribute to no class, gives the cells of ykpred_preempt_round;
+ *   (3) at limit 0, W repeats of an ask that ykpred_headroom_spread (ykpred_headroom_affinity) answers with status 0 place exactly
+ *   min(W, its copies).
+ * Errors as ykpred_preempt_round; additionally YKPRED_E_UNSUPPORTED without spec effects of the current spec table, YKPRED_E_STATE
+ *   without a victim-effects plane that describes the resident victim table (none uploaded, dropped by ykpred_set_victims, or a segment
+ *   patched without its plane rows). ONE query; roctx range "ykpred:preempt_round_live"; plain launches on the engine's stream: per
+ *   evaluated ask the step and the apply, then k_preempt_round_effects (thread = constraint, a dense [2][G] int record zeroed on the
+ *   stream first) and k_preempt_round_topo (a workgroup per constraint, at work where the record names a step).
+ * NODE-SHARDED engines: COLLECTIVE; the agreement covers the new arguments; per applied turn ONE all-reduce SUM of the record between
+ *   the two kernels (the owner of the node fills it, the others contribute zeros); every rank moves its cluster-wide copy. The record
+ *   is dense: no cap on the constraints one turn moves. A rank whose shard holds no node takes part in every reduce. The histograms must be current (ykpred_eval) as for every sharded query. */
+/* out2 = { layout.spread_cells, G = constraints of all topology signatures } for the current tables: the sizes of out_counts / out_minima.
+ * Builds the signature tables when they are stale (no device pass); YKPRED_E_STATE before the node and spec tables are uploaded. */
+int32_t ykpred_histogram_dims(ykpred_engine_t* e, int64_t* out2 /* [2] */);
+int32_t ykpred_preempt_round_live(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks /* host, ask indices, list order, repeats = copies */,
+                                  const int32_t* limits /* host, [n_asks], 0..T */, uint32_t prefilter_plugins, uint32_t filter_plugins,
+                                  int64_t* out_cells /* host, [n_asks][YKPRED_PREEMPT_ROUND_CELLS] */, int64_t* out_summary /* host, [8] */,
+                                  int32_t* out_counts /* host, NULL or [layout.spread_cells] */, int32_t* out_minima /* host, NULL or [G] */);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Multi-GPU: node-axis shards. One engine per GPU / process holds a contiguous shard of the node table and

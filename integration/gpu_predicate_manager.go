@@ -744,6 +744,20 @@ type PreemptionPlan struct {
 // one scheduling cycle: it replaces the per-ask loop PreemptionVictims → RemovePod per victim → AssumePod. ok == false when a pod is not
 // a mirrored ask, no tiers are set or the engine failed: the caller plans ask by ask as before.
 func (m *gpuPredicateManager) PreemptionRound(pods []*v1.Pod) (plans []PreemptionPlan, victimsInAll int64, ok bool) {
+	return m.preemptionRound(pods, false)
+}
+
+// PreemptionRoundLive is PreemptionRound for lists that hold asks with a hard topology spread, required pod affinity or anti-affinity
+// (ykhost_preempt_round_live_by_keys, ONE crossing): no ask comes back with Outcome 4. Every ask takes its turn against the
+// PodTopologySpread / InterPodAffinity match counts as the earlier placements AND the earlier victims of the list left them — a claimed
+// victim leaves the counts as RemovePod would take it out, a placed ask enters them as AssumePod would. The call site is
+// PreemptionRound's, for queues whose starved asks carry such constraints (a gang with a zone spread, "one per host" executors, workers
+// that must land beside their driver): it replaces the loop that rebuilt the histograms between every two asks.
+func (m *gpuPredicateManager) PreemptionRoundLive(pods []*v1.Pod) (plans []PreemptionPlan, victimsInAll int64, ok bool) {
+	return m.preemptionRound(pods, true)
+}
+
+func (m *gpuPredicateManager) preemptionRound(pods []*v1.Pod, live bool) (plans []PreemptionPlan, victimsInAll int64, ok bool) {
 	n := len(pods)
 	if n == 0 {
 		return nil, 0, true
@@ -770,8 +784,14 @@ func (m *gpuPredicateManager) PreemptionRound(pods []*v1.Pod) (plans []Preemptio
 	for {
 		names := (*C.char)(C.malloc(C.size_t(namesLen)))
 		uids := (*C.char)(C.malloc(C.size_t(uidsLen)))
-		rc := C.ykhost_preempt_round_by_keys(m.host, C.int32_t(n), (**C.char)(unsafe.Pointer(&keys[0])), &cells[0], &summary[0], names, namesLen,
-			uids, uidsLen, &needed[0])
+		var rc C.int32_t
+		if live {
+			rc = C.ykhost_preempt_round_live_by_keys(m.host, C.int32_t(n), (**C.char)(unsafe.Pointer(&keys[0])), &cells[0], &summary[0], names, namesLen,
+				uids, uidsLen, &needed[0])
+		} else {
+			rc = C.ykhost_preempt_round_by_keys(m.host, C.int32_t(n), (**C.char)(unsafe.Pointer(&keys[0])), &cells[0], &summary[0], names, namesLen,
+				uids, uidsLen, &needed[0])
+		}
 		if rc == 0 && (needed[0] > namesLen || needed[1] > uidsLen) { // (the round starts from zero state: asking again is exact)
 			C.free(unsafe.Pointer(names))
 			C.free(unsafe.Pointer(uids))

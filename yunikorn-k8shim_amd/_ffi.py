@@ -55,6 +55,10 @@ class YkpredVictims(C.Structure):
                 ("cum", C.c_void_p), ("ports_after", C.c_void_p)]
 
 
+class YkpredVictimEffects(C.Structure):
+    _fields_ = [("classes", C.c_int32), ("columns", C.c_int32), ("rows", C.c_int64), ("class_col", C.c_void_p), ("cum", C.c_void_p)]
+
+
 MAX_TIMED = 24
 
 
@@ -163,6 +167,11 @@ def load_ykpred():
     L.ykpred_preempt_victims.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     L.ykpred_preempt_victims_pod.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
     L.ykpred_preempt_round.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.ykpred_preempt_round_live.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]
+    L.ykpred_histogram_dims.argtypes = [C.c_void_p, C.c_void_p]
+    L.ykpred_set_victim_effects.argtypes = [C.c_void_p, C.POINTER(YkpredVictimEffects)]
+    L.ykpred_update_victim_effects_node.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     L.ykpred_preempt_headroom.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     L.ykpred_preempt_headroom_pod.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
     _pred = L
@@ -270,6 +279,13 @@ def load_ykhost():
     L.ykhost_preempt_gang_by_key.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                              C.c_void_p]
     L.ykhost_victim_range.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.ykhost_preempt_round_live.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                            C.c_void_p]
+    L.ykhost_preempt_round_live_by_keys.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                    C.c_int64, C.c_void_p]
+    L.ykhost_preempt_gang_live_by_key.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                  C.c_int64, C.c_void_p]
+    L.ykhost_victim_effects.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ykhost_preempt_headroom.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ykhost_preempt_headroom_nodes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.ykhost_preempt_headroom_by_key.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p]

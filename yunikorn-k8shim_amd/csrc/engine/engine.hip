@@ -296,6 +296,12 @@ struct ykpred_engine {
   bool vt_ports = false;
   int64_t vt_max_cap = 0;  // the longest segment's capacity (ykpred_preempt_round packs a prefix length into 28 bits)
   DevBuf d_pround;         // ykpred_preempt_round: [asks][8] cells | [asks] best keys | [asks][2] counts | the round's state columns
+  // the victim-effects plane beside the victim table (ykpred_set_victim_effects): what every victim prefix contributed to the selector classes
+  DevBuf d_vfx_col, d_vfx_cum;            // [KS] int column of a class or -1; [KA][P] int prefix sums per segment
+  int vfx_columns = -1;                   // KA; -1 = no plane (ykpred_set_victims drops it)
+  std::vector<uint8_t> vfx_stale;         // [N] the node's segment was rewritten (ykpred_update_victims_node) and its plane rows were not
+  int64_t vfx_stale_nodes = 0;
+  DevBuf d_pround_live;                   // ykpred_preempt_round_live: steps | cnt [cells] | minv, mn, at_min, nd [G] each | record [2][G]
   DevBuf d_bytes_gather;  // ykpred_comm_allgather_bytes
   DevBuf d_topo_agree;  // node-sharded: the shape of every rank's topology histograms (agree_topology)
   u64 dict_digest = 0;  // ykpred_set_dictionary_digest
@@ -1343,6 +1349,12 @@ int build_spread_tables(ykpred_engine* e, hipStream_t st) {
   TRY(upload(e, e->d_sp_c, rows.data(), rows.size(), st));
   TRY(upload(e, e->d_sp_aff, aff.data(), aff.size(), st));
   TRY(upload(e, e->d_sp_tol, tol.data(), tol.size(), st));
+  {  // constraint → signature, for the eligibility test of the node a pod lands on (ykpred_preempt_round_live; an allocation round uploads its own)
+    std::vector<int32_t> sig_of;
+    for (size_t d = 0; d < e->spread_sig.size(); ++d) sig_of.insert(sig_of.end(), e->spread_sig[d].size(), (int32_t)d);
+    sig_of.resize(std::max<size_t>(rows.size(), 1), 0);
+    TRY(upload(e, e->d_sp_sig_of, sig_of.data(), sig_of.size(), st));  // (the synchronise below covers the local)
+  }
   HIPCHK(e->d_sp_cnt.ensure((size_t)std::max<int64_t>(cells, 1) * sizeof(int)));
   HIPCHK(e->d_sp_present.ensure((size_t)std::max<int64_t>(cells, 1) * sizeof(int)));
   HIPCHK(e->d_sp_min.ensure((size_t)std::max(e->spread_constraints, 1) * sizeof(int)));
@@ -1864,6 +1876,7 @@ int32_t ykpred_set_nodes(ykpred_engine_t* e, const ykpred_nodes_t* n) {
     e->base_ranked.release();
     e->rc_tiers = 0;  // the reclaim table describes N nodes
     e->vt_tiers = 0;  // and so does the victim table
+    e->vfx_columns = -1;  // (with its effects plane)
   }
   e->N = n->count;
   e->row_words = (e->N + 63) / 64;
@@ -4913,6 +4926,7 @@ int32_t ykpred_set_victims(ykpred_engine_t* e, const ykpred_victims_t* vt) {
   Range roctx_range("ykpred:upload_victims");
   if (!e) return YKPRED_E_INVALID;
   e->n_uploads++;
+  e->vfx_columns = -1;  // (the effects plane describes the rows of ONE victim table)
   if (!vt) {
     e->vt_tiers = 0;
     return YKPRED_OK;
@@ -4974,6 +4988,57 @@ int32_t ykpred_update_victims_node(ykpred_engine_t* e, int32_t idx, int32_t coun
         HIPCHK(hipMemcpyAsync(e->d_vt_ports.as<u64>() + (size_t)k * P + base, one->ports_after + (size_t)k * c, c * sizeof(u64), hipMemcpyHostToDevice, st));
   }
   HIPCHK(hipStreamSynchronize(st));
+  if (e->vfx_columns >= 0 && (size_t)idx < e->vfx_stale.size() && !e->vfx_stale[(size_t)idx]) e->vfx_stale[(size_t)idx] = 1, e->vfx_stale_nodes++;
+  return YKPRED_OK;
+}
+
+// The victim-effects plane: beside the victim table, row for row. Checked here: the kernel reads rows base + from - 1
+// and base + from + extra - 1 of a column class_col names, both inside the segment ykpred_set_victims checked.
+int32_t ykpred_set_victim_effects(ykpred_engine_t* e, const ykpred_victim_effects_t* fx) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:upload_victim_effects");
+  if (!e) return YKPRED_E_INVALID;
+  e->n_uploads++;
+  e->vfx_columns = -1;
+  if (!fx) return YKPRED_OK;
+  if (!e->nodes_set || e->vt_tiers == 0) return fail(e, YKPRED_E_STATE, "set_victim_effects: no victim table (ykpred_set_victims)");
+  if (fx->rows != (int64_t)e->vt_rows || fx->classes != e->KS)
+    return fail(e, YKPRED_E_INVALID, "set_victim_effects: the plane must have the victim table's rows and the node table's selector classes");
+  if (fx->columns < 0 || fx->columns > fx->classes || (fx->classes > 0 && !fx->class_col) || (fx->columns > 0 && fx->rows > 0 && !fx->cum))
+    return fail(e, YKPRED_E_INVALID, "set_victim_effects: bad argument");
+  for (int s = 0; s < fx->classes; ++s)
+    if (fx->class_col[s] < -1 || fx->class_col[s] >= fx->columns) return fail(e, YKPRED_E_INVALID, "set_victim_effects: class_col outside -1 .. columns - 1");
+  HIPCHK(hipSetDevice(e->cfg.device));
+  hipStream_t st = e->own_stream;
+  const int32_t none = -1;
+  TRY(upload(e, e->d_vfx_col, fx->classes > 0 ? fx->class_col : &none, (size_t)std::max(fx->classes, 1), st));
+  HIPCHK(e->d_vfx_cum.ensure(std::max<size_t>((size_t)fx->columns * e->vt_rows, 1) * sizeof(int32_t)));
+  if ((size_t)fx->columns * e->vt_rows > 0)
+    HIPCHK(hipMemcpyAsync(e->d_vfx_cum.p, fx->cum, (size_t)fx->columns * e->vt_rows * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  e->vfx_stale.assign((size_t)e->N, 0);
+  e->vfx_stale_nodes = 0;
+  e->vfx_columns = fx->columns;
+  return YKPRED_OK;
+}
+
+int32_t ykpred_update_victim_effects_node(ykpred_engine_t* e, int32_t idx, int32_t count, const int32_t* cum) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:update_victim_effects_node");
+  if (!e || count < 0) return fail(e, YKPRED_E_INVALID, "update_victim_effects_node: bad argument");
+  e->n_uploads++;
+  if (!e->nodes_set || e->vt_tiers == 0 || e->vfx_columns < 0) return fail(e, YKPRED_E_STATE, "update_victim_effects_node: no victim-effects plane");
+  if (idx < 0 || idx >= e->N) return fail(e, YKPRED_E_INVALID, "update_victim_effects_node: index out of range");
+  if (count > e->h_vt_cap[(size_t)idx]) return fail(e, YKPRED_E_INVALID, "update_victim_effects_node: count passes the segment's capacity");
+  if (count > 0 && e->vfx_columns > 0 && !cum) return fail(e, YKPRED_E_INVALID, "update_victim_effects_node: bad argument");
+  HIPCHK(hipSetDevice(e->cfg.device));
+  hipStream_t st = e->own_stream;
+  const size_t P = e->vt_rows, base = (size_t)e->h_vt_base[(size_t)idx], c = (size_t)count;
+  if (c > 0)
+    for (int k = 0; k < e->vfx_columns; ++k)
+      HIPCHK(hipMemcpyAsync(e->d_vfx_cum.as<int32_t>() + (size_t)k * P + base, cum + (size_t)k * c, c * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (e->vfx_stale[(size_t)idx]) e->vfx_stale[(size_t)idx] = 0, e->vfx_stale_nodes--;
   return YKPRED_OK;
 }
 
@@ -5039,35 +5104,60 @@ int32_t ykpred_preempt_victims_pod(ykpred_engine_t* e, int32_t pod, int32_t limi
 // Victim plans for a list of asks, conflict-resolved: per ask one k_preempt_round_step over every node and one
 // k_preempt_round_apply wave, queued back to back on the engine's stream with the round's zeroed state columns between them; one
 // readback at the end. ask_query_prepare does the checks and the agreement; its tasks are not used (every occurrence is its own turn).
-int32_t ykpred_preempt_round(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, const int32_t* limits, uint32_t pre, uint32_t filt,
-                             int64_t* out_cells, int64_t* out_summary) {
-  YK_SERIALISE(e);
-  Range roctx_range("ykpred:preempt_round");
-  if (e) e->n_queries++;
+// `live` (ykpred_preempt_round_live, §4.20): no ask is settled as coupled; the step reads the round's own copy of the topology
+// histograms, and behind every turn k_preempt_round_effects / k_preempt_round_topo move that copy by what the placed pod adds and the
+// claimed victims took along.
+static int32_t preempt_round_run(ykpred_engine_t* e, bool live, int32_t n_asks, const int32_t* asks, const int32_t* limits, uint32_t pre, uint32_t filt,
+                                 int64_t* out_cells, int64_t* out_summary, int32_t* out_counts, int32_t* out_minima) {
+  const std::string name = live ? "preempt_round_live" : "preempt_round";
   static_assert(ykk::kPreemptRoundCells == YKPRED_PREEMPT_ROUND_CELLS, "k_preempt_round_apply writes the layout of ykpred.h");
   constexpr size_t B = YKPRED_PREEMPT_ROUND_CELLS;
   if (!e) return YKPRED_E_INVALID;
   const bool args_ok = out_summary && (n_asks <= 0 || (asks && limits && out_cells));
   auto more_checks = [&](std::string* why) -> int {
-    if (e->vt_tiers == 0 || e->vt_tiers != e->rc_tiers) return *why = "preempt_round: no victim table (ykpred_set_victims)", YKPRED_E_STATE;
-    if (e->vt_max_cap > ykk::kReachPodsMax) return *why = "preempt_round: a segment of more than 2^28 - 1 rows", YKPRED_E_UNSUPPORTED;
+    if (e->vt_tiers == 0 || e->vt_tiers != e->rc_tiers) return *why = name + ": no victim table (ykpred_set_victims)", YKPRED_E_STATE;
+    if (e->vt_max_cap > ykk::kReachPodsMax) return *why = name + ": a segment of more than 2^28 - 1 rows", YKPRED_E_UNSUPPORTED;
     for (int i = 0; i < n_asks; ++i)
-      if (limits[i] < 0 || limits[i] > e->vt_tiers) return *why = "preempt_round: limit outside 0 .. tiers", YKPRED_E_INVALID;
+      if (limits[i] < 0 || limits[i] > e->vt_tiers) return *why = name + ": limit outside 0 .. tiers", YKPRED_E_INVALID;
+    if (!live) return YKPRED_OK;
+    if (e->fx_version != e->specs_version)
+      return *why = name + ": the specs' effects are not uploaded for the current spec table (ykpred_set_spec_effects): what a placed pod adds to the histograms is unknown", YKPRED_E_UNSUPPORTED;
+    if (e->vfx_columns < 0 || e->vfx_stale_nodes > 0)
+      return *why = name + ": no victim-effects plane for the resident victim table (ykpred_set_victim_effects / ykpred_update_victim_effects_node): what a claimed victim takes out of the histograms is unknown", YKPRED_E_STATE;
+    // (the round copies the histograms whatever the lists name; a sharded engine cannot rebuild its cluster-wide sums behind the agreement)
+    if (e->comm && e->comm_world > 1 && e->N > 0 && n_asks > 0) {
+      if (e->spread_dirty) TRY(build_spread_tables(e, e->own_stream));
+      if (e->fam_spread.D > 0 && e->hist_epoch != e->nodes_epoch)
+        return *why = name + ": topology histograms are stale on a sharded engine: run ykpred_eval on every shard first", YKPRED_E_STATE;
+    }
     return YKPRED_OK;
   };
   // (the plugin lists too: which asks are settled as coupled — and so which all-reduces are issued — depends on them)
-  u64 more = tune_hash({(u64)(uint32_t)e->vt_tiers, 0x726f756eull, (u64)pre, (u64)filt});
+  u64 more = tune_hash({(u64)(uint32_t)e->vt_tiers, live ? 0x6c697665ull : 0x726f756eull, (u64)pre, (u64)filt});
+  if (live) more = tune_hash({(u64)(out_counts != nullptr), (u64)(out_minima != nullptr), (u64)(uint32_t)e->spread_constraints, (u64)e->spread_cells}, more);
   if (n_asks > 0 && args_ok)
     for (int i = 0; i < n_asks; ++i) more = tune_hash({(u64)(uint32_t)limits[i]}, more);
   AskTasks tasks;
   tasks.need_fit = false;
   tasks.other_causes = "bad argument, no victim table, a limit outside 0 .. tiers, tables not uploaded, an index out of range or stale topology histograms";
   bool run = false;
-  const int32_t rc = ask_query_prepare(e, "preempt_round", n_asks, asks, args_ok, pre, filt, more_checks, more, &tasks, &run);
+  const int32_t rc = ask_query_prepare(e, name, n_asks, asks, args_ok, pre, filt, more_checks, more, &tasks, &run);
   if (out_summary && (run || rc == YKPRED_OK)) std::fill(out_summary, out_summary + B, (int64_t)0);
-  if (!run) return rc;
   const bool sharded = e->comm && e->comm_world > 1;
   hipStream_t st = e->own_stream;
+  if (live && rc == YKPRED_OK && (out_counts || out_minima)) {
+    // (an empty list, or no node: the round-local histograms are the engine's — when those are current)
+    if (!run || e->N == 0) {
+      if (e->nodes_set && e->specs_set && e->spread_dirty) TRY(build_spread_tables(e, st));
+      if (!sharded && e->nodes_set && e->specs_set && e->N > 0) TRY(ensure_histograms(e, st));
+      if (out_counts && e->spread_cells > 0) HIPCHK(hipMemcpyAsync(out_counts, e->d_sp_cnt.p, (size_t)e->spread_cells * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+      if (out_minima && e->spread_constraints > 0) HIPCHK(hipMemcpyAsync(out_minima, e->d_sp_min.p, (size_t)e->spread_constraints * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      out_counts = out_minima = nullptr;
+    }
+  }
+  if (!run) return rc;
+  if (live && !sharded && e->N > 0) TRY(ensure_histograms(e, st));  // (lists without a topology plugin: ask_query_prepare left them as they were)
   const size_t A = (size_t)n_asks, N = (size_t)e->N, R = (size_t)e->R, KP = (size_t)e->KP;
   // one buffer: cells [A][8] | best keys [A] | counts [A][2] | placed_req [R][N] | placed_ports [KP][N] | taken [N] | placed_pods [N]
   const size_t state_bytes = (R + KP) * N * sizeof(int64_t) + 2 * N * sizeof(int32_t);
@@ -5087,13 +5177,46 @@ int32_t ykpred_preempt_round(ykpred_engine_t* e, int32_t n_asks, const int32_t* 
   const ykk::VictimTable vt = victim_table(e);
   const int offset = sharded ? e->node_offset : 0;
   const dim3 grid((unsigned)((N + ykk::kBlock - 1) / ykk::kBlock));
+  // live: steps | cnt [cells] | minv [G] | mn [G] | at_min [G] | nd [G] | record [2][G] — the copies taken from the prepared histograms
+  const size_t G = live ? (size_t)e->spread_constraints : 0, HC = live ? (size_t)e->spread_cells : 0;
+  ykk::SpecTable live_tab = stab;
+  unsigned long long* d_steps = nullptr;
+  int *l_mn = nullptr, *l_at = nullptr, *l_nd = nullptr, *l_rec = nullptr;
+  ykk::VictimEffects ve{};
+  ykk::SpecEffects fx{};
+  ykk::AffSigs sig_aff{};
+  if (live) {
+    HIPCHK(e->d_pround_live.ensure(sizeof(int64_t) + (HC + 6 * G + 16) * sizeof(int32_t)));
+    d_steps = e->d_pround_live.as<unsigned long long>();
+    int* l_cnt = (int*)(d_steps + 1);
+    int* l_minv = l_cnt + HC;
+    l_mn = l_minv + G, l_at = l_mn + G, l_nd = l_at + G, l_rec = l_nd + G;
+    HIPCHK(hipMemsetAsync(d_steps, 0, sizeof(int64_t), st));
+    if (HC) HIPCHK(hipMemcpyAsync(l_cnt, e->d_sp_cnt.p, HC * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    if (G) HIPCHK(hipMemcpyAsync(l_minv, e->d_sp_min.p, G * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    live_tab.spread.cnt = l_cnt;
+    live_tab.spread.minv = l_minv;
+    if (G) {  // (d_sp_sig_of: build_spread_tables uploaded it with the signature tables)
+      hipLaunchKernelGGL(ykk::k_round_topo_init, dim3((unsigned)G), dim3(ykk::kWave), 0, st, live_tab.spread, (int)G, l_mn, l_at, l_nd);
+      HIPCHK(hipGetLastError());
+    }
+    sig_aff = ykk::AffSigs{e->d_sig_aff_flags.as<unsigned>(), e->d_sig_aff_off.as<int>(), e->d_sig_aff_terms.as<u64>(), e->d_sig_pre_off.as<int>(),
+                           e->d_sig_pre_terms.as<u64>()};
+    ve.KA = e->vfx_columns;
+    ve.class_col = e->d_vfx_col.as<int>();
+    ve.cum = e->d_vfx_cum.as<int>();
+    fx.off = e->fx_contrib ? e->d_fx_off.as<int>() : nullptr;
+    fx.cls = e->d_fx_cls.as<int>();
+    fx.cnt = e->d_fx_cnt.as<int>();
+  }
+  const ykk::SpecTable& step_tab = live ? live_tab : stab;
   for (size_t i = 0; i < A; ++i) {
     const int32_t a = asks[i], spec = e->h_pod_spec[(size_t)a], pin = e->h_pod_pin[(size_t)a];
     int settled = 0;
     if ((size_t)spec < e->h_sflags.size() && (e->h_sflags[(size_t)spec] & YKPRED_SPEC_UNSUPPORTED)) settled = 3;
-    else if (headroom_coupled(e, spec, pre, filt)) settled = 4;
+    else if (!live && headroom_coupled(e, spec, pre, filt)) settled = 4;
     if (!settled && N > 0) {
-      hipLaunchKernelGGL(ykk::k_preempt_round_step, grid, dim3(ykk::kBlock), 0, st, nt, stab, vt, rs, spec, pin, limits[i], offset, pre, filt,
+      hipLaunchKernelGGL(ykk::k_preempt_round_step, grid, dim3(ykk::kBlock), 0, st, nt, step_tab, vt, rs, spec, pin, limits[i], offset, pre, filt,
                          (ykk::u64*)(d_best + i), (ykk::i64*)(d_counts + 2 * i));
       HIPCHK(hipGetLastError());
     }
@@ -5104,11 +5227,33 @@ int32_t ykpred_preempt_round(ykpred_engine_t* e, int32_t n_asks, const int32_t* 
     hipLaunchKernelGGL(ykk::k_preempt_round_apply, dim3(1), dim3(ykk::kWave), 0, st, nt, stab, rs, spec, limits[i], settled, offset,
                        (const ykk::u64*)(d_best + i), (const ykk::i64*)(d_counts + 2 * i), (ykk::i64*)(d_cells + i * B));
     HIPCHK(hipGetLastError());
+    if (live && !settled && G > 0 && (N > 0 || sharded)) {
+      // the turn's step of the histograms: the owner of the node fills the dense record, every rank applies it to its cluster-wide copy.
+      // A rank whose shard holds no node launches no effects kernel but takes part in the reduce (as in the MIN / SUM above): the
+      // collectives pair up on every rank
+      HIPCHK(hipMemsetAsync(l_rec, 0, 2 * G * sizeof(int32_t), st));
+      if (N > 0) {
+        hipLaunchKernelGGL(ykk::k_preempt_round_effects, dim3((unsigned)((G + ykk::kBlock - 1) / ykk::kBlock)), dim3(ykk::kBlock), 0, st, nt, live_tab.spread,
+                           sig_aff, e->d_sig_tol.as<u64>(), e->d_sp_sig_of.as<int>(), (int)G, vt, ve, fx, spec, offset, (const ykk::i64*)(d_cells + i * B), l_rec);
+        HIPCHK(hipGetLastError());
+      }
+      if (sharded) NCCLCHK(rccl()->AllReduce(l_rec, l_rec, 2 * G, ncclInt32, ncclSum, e->comm, st));
+      hipLaunchKernelGGL(ykk::k_preempt_round_topo, dim3((unsigned)G), dim3(ykk::kBlock), 0, st, live_tab.spread, (int)G, (const int*)l_rec, l_mn, l_at,
+                         (const int*)l_nd, d_steps);
+      HIPCHK(hipGetLastError());
+    }
   }
   // (cell [2] is the owner's alone and 0 elsewhere, every other cell is the same on all ranks: one MAX makes the tables equal)
   if (sharded) NCCLCHK(rccl()->AllReduce(d_cells, d_cells, A * B, ncclInt64, ncclMax, e->comm, st));
   HIPCHK(hipMemcpyAsync(out_cells, d_cells, A * B * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  int64_t steps = 0;
+  if (live) {
+    HIPCHK(hipMemcpyAsync(&steps, d_steps, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (out_counts && HC) HIPCHK(hipMemcpyAsync(out_counts, live_tab.spread.cnt, HC * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (out_minima && G) HIPCHK(hipMemcpyAsync(out_minima, live_tab.spread.minv, G * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  }
   HIPCHK(hipStreamSynchronize(st));
+  out_summary[7] = steps;
   std::vector<int64_t> touched;
   for (size_t i = 0; i < A; ++i) {
     const int64_t* c = out_cells + i * B;
@@ -5119,6 +5264,37 @@ int32_t ykpred_preempt_round(ykpred_engine_t* e, int32_t n_asks, const int32_t* 
   std::sort(touched.begin(), touched.end());
   out_summary[6] = (int64_t)(std::unique(touched.begin(), touched.end()) - touched.begin());
   return YKPRED_OK;
+}
+
+// the sizes of ykpred_preempt_round_live's readback: { layout.spread_cells, G } for the current tables
+int32_t ykpred_histogram_dims(ykpred_engine_t* e, int64_t* out2) {
+  YK_SERIALISE(e);
+  if (!e || !out2) return fail(e, YKPRED_E_INVALID, "histogram_dims: bad argument");
+  out2[0] = out2[1] = 0;
+  if (!e->nodes_set || !e->specs_set) return fail(e, YKPRED_E_STATE, "histogram_dims: tables not uploaded");
+  HIPCHK(hipSetDevice(e->cfg.device));
+  if (e->spread_dirty) TRY(build_spread_tables(e, e->own_stream));
+  out2[0] = e->spread_cells;
+  out2[1] = e->spread_constraints;
+  return YKPRED_OK;
+}
+
+int32_t ykpred_preempt_round(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, const int32_t* limits, uint32_t pre, uint32_t filt,
+                             int64_t* out_cells, int64_t* out_summary) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:preempt_round");
+  if (e) e->n_queries++;
+  return preempt_round_run(e, false, n_asks, asks, limits, pre, filt, out_cells, out_summary, nullptr, nullptr);
+}
+
+// The round with the topology histograms kept live: the same launches, and per applied turn k_preempt_round_effects,
+// (sharded: one SUM all-reduce of the dense [2][G] record) and k_preempt_round_topo.
+int32_t ykpred_preempt_round_live(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, const int32_t* limits, uint32_t pre, uint32_t filt,
+                                  int64_t* out_cells, int64_t* out_summary, int32_t* out_counts, int32_t* out_minima) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:preempt_round_live");
+  if (e) e->n_queries++;
+  return preempt_round_run(e, true, n_asks, asks, limits, pre, filt, out_cells, out_summary, out_counts, out_minima);
 }
 
 // Headroom per GROUP of nodes (a zone, a rack, a host): the replicas of ykpred_headroom summed per group id of a caller-given column

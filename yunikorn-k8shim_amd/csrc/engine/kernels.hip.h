@@ -4597,6 +4597,103 @@ __global__ __launch_bounds__(kWave) void k_round_topo_init(SpreadSigs sp, int n_
     nd_out[g] = nd;
   }
 }
+// ykpred_preempt_round_live: the preemption round with the PreFilter state of the topology plugins kept LIVE. The
+// step and the apply are ykpred_preempt_round's, launched unchanged — the step's SpecTable points at the round's copies of cnt / minv.
+// Behind an applied turn two kernels move those copies: what the placed pod adds to every selector class (SpecEffects) minus what the
+// claimed victims order(n)[from .. from + extra) contributed to it — two cells of the victim-effects plane, prefix sums per segment
+// like cum.
+struct VictimEffects {
+  int KA;                // columns of the plane: the selector classes some eligible pod contributes to
+  const int* class_col;  // [KS] column of a selector class, -1 = none
+  const int* cum;        // [KA][vt.rows] PREFIX sums of the victims' contributions within the segment
+};
+// thread = constraint g (of any signature), on every rank; only the rank that owns the turn's node writes. rec = [2][G] ints, zeroed on
+// the stream before the launch: rec[g] = delta_g, rec[G + g] = the node's domain of g's key — written only where delta_g != 0 and a
+// pod on the node counts for g (k_allocate_round's assume test). `cells` are the turn's cells as k_preempt_round_apply left them
+// ([2], from, is the owner's).
+__global__ __launch_bounds__(kBlock) void k_preempt_round_effects(NodeTable t, SpreadSigs sp, AffSigs sig_aff, const u64* __restrict__ sig_tol,
+                                                                  const int* __restrict__ sig_of, int G, VictimTable vt, VictimEffects ve,
+                                                                  SpecEffects fx, int spec, int node_offset, const i64* __restrict__ cells,
+                                                                  int* __restrict__ rec) {
+  const int g = blockIdx.x * kBlock + threadIdx.x;
+  if (g >= G) return;
+  if (cells[0] < 0 || cells[0] > 1) return;  // (nowhere, unsupported: nothing was applied)
+  const i64 local = cells[1] - node_offset;
+  if (local < 0 || local >= t.n) return;
+  const int n = (int)local;
+  const SpreadC c = sp.c[g];
+  if (c.ks < 0) return;
+  int v = 0;
+  if (fx.off)
+    for (int k = fx.off[spec]; k < fx.off[spec + 1]; ++k)
+      if (fx.cls[k] == c.ks) v = fx.cnt[k];
+  const i64 from = cells[2], extra = cells[3];
+  const int col = ve.class_col[c.ks];
+  if (extra > 0 && col >= 0) {
+    const int* row = ve.cum + (size_t)col * vt.rows + (size_t)vt.seg_base[n];
+    v -= row[from + extra - 1] - (from > 0 ? row[from - 1] : 0);
+  }
+  if (v == 0) return;
+  const int dom = t.domain[(size_t)c.kd * t.n + n];
+  if (dom < 0 || dom >= c.dom_size) return;
+  if (c.kind == kKindSpread && !spread_counts_here(c, spread_eligibility(t, sp, sig_aff, sig_tol, sig_of[g], n))) return;
+  rec[g] = v;
+  rec[G + g] = dom;
+}
+// a workgroup per constraint, at work only where rec names a step: the cell moves by delta_g (either sign); a spread constraint's
+// minimum over the present domains, the domains at the minimum and its minv after the minDomains rule are recomputed whole (what
+// k_round_apply_deltas does per entry); an InterPodAffinity row's minv — the domains with a match — moves by one when the cell crosses
+// zero, in either direction. *changed counts the steps. Every rank of a sharded engine runs it on its cluster-wide copy.
+// (mn_out / at_min_out are the round state the contract names, kept as k_allocate_round keeps it; this kernel recomputes a row whole and reads
+// neither — only nd, which no step changes.)
+__global__ __launch_bounds__(kBlock) void k_preempt_round_topo(SpreadSigs hist, int G, const int* __restrict__ rec, int* __restrict__ mn_out,
+                                                               int* __restrict__ at_min_out, const int* __restrict__ nd,
+                                                               unsigned long long* __restrict__ changed) {
+  __shared__ int sh_mn[kWavesPerBlock], sh_at[kWavesPerBlock];
+  const int g = blockIdx.x;
+  if (g >= G) return;
+  const int v = rec[g];
+  if (v == 0) return;  // (the whole workgroup alike)
+  const int tid = threadIdx.x, lane = tid % kWave, wave = tid / kWave;
+  const SpreadC c = hist.c[g];
+  const int dom = rec[G + g];
+  if (dom < 0 || dom >= c.dom_size) return;
+  const int old = hist.cnt[c.cnt_off + dom], now = old + v;
+  __syncthreads();  // (everybody has read the old count)
+  if (tid == 0) {
+    hist.cnt[c.cnt_off + dom] = now;
+    atomicAdd(changed, 1ull);
+  }
+  if (c.kind != kKindSpread) {
+    if (tid == 0 && old <= 0 && now > 0) hist.minv[g] = hist.minv[g] + 1;
+    if (tid == 0 && old > 0 && now <= 0) hist.minv[g] = hist.minv[g] - 1;
+    return;
+  }
+  int mn = 0x7fffffff;
+  for (int d = tid; d < c.dom_size; d += kBlock)
+    if (hist.present[c.cnt_off + d]) mn = min(mn, d == dom ? now : hist.cnt[c.cnt_off + d]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mn = min(mn, __shfl_xor(mn, off, kWave));
+  if (lane == 0) sh_mn[wave] = mn;
+  __syncthreads();
+  mn = sh_mn[0];
+#pragma unroll
+  for (int q = 1; q < kWavesPerBlock; ++q) mn = min(mn, sh_mn[q]);
+  int at = 0;
+  for (int d = tid; d < c.dom_size; d += kBlock)
+    at += (hist.present[c.cnt_off + d] && (d == dom ? now : hist.cnt[c.cnt_off + d]) == mn) ? 1 : 0;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) at += __shfl_xor(at, off, kWave);
+  if (lane == 0) sh_at[wave] = at;
+  __syncthreads();
+  if (tid == 0) {
+    at = 0;
+    for (int q = 0; q < kWavesPerBlock; ++q) at += sh_at[q];
+    mn_out[g] = mn;
+    at_min_out[g] = at;
+    hist.minv[g] = nd[g] < c.min_domains ? 0 : mn;
+  }
+}
 // The kernel's tables are a hundred pointers. Taken as ordinary arguments they are all loaded at entry and stay live through the
 // loop: twice the scalar register file, spilled to vector lanes and those to scratch — every reload a full wait in the middle of a
 // load round. So the loop reads them where it uses them, from the kernel-argument segment itself (scalar loads, constant cache),

@@ -789,6 +789,19 @@ class Encoder {
     return known;
   }
 
+  // What ONE pod on a node adds to count class s: the term encode_node_spread sums over the node's pods (a terminating pod adds
+  // nothing to a PodTopologySpread class). The victim-effects plane is made of these.
+  int pod_class_contribution(int s, const Pod& p) {
+    const SelectorClass& sc = sel_classes[(size_t)s];
+    if (sc.kind == SelectorClass::kSpread && p.terminating) return 0;
+    auto key = std::make_pair(p.tpl, s);
+    auto m = sel_memo_.find(key);
+    if (m != sel_memo_.end()) return m->second;
+    const int contrib = class_contribution(sc, *p.tpl);
+    sel_memo_.emplace(key, contrib);
+    return contrib;
+  }
+
   // ---- node rows -----------------------------------------------------------------------------------
   typedef std::unordered_map<std::string, std::vector<uint64_t>> LabelMemo;
   // memo: the label-tuple cache to use — null = the encoder's own (single-threaded callers); the parallel node loop of a full

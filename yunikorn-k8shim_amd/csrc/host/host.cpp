@@ -272,6 +272,18 @@ struct ykhost {
     std::vector<int64_t> cum;                  // [R][P]
     std::vector<uint64_t> ports;               // [KP][P]
     int64_t derived = 0, patches = 0;
+    // the victim-effects plane (ykhost_preempt_round_live): nothing is derived before the first live call; from then on it is derived with
+    // the table, patched with the segments of changed nodes and derived anew when the selector classes move or a class gains its first
+    // contributing victim
+    bool fx_on = false, fx_built = false, fx_on_device = false;
+    uint64_t fx_digest = 0;  // the topology dictionaries (selector classes among them) the columns were chosen under
+    size_t KS = 0, KA = 0, fx_P = 0;
+    std::vector<int32_t> class_col;  // [KS] column of a class, -1: no eligible pod contributes to it
+    std::vector<int32_t> fx_cum;     // [KA][P]
+    std::vector<int> fx_to_push;
+    std::vector<int> fx_pending;  // nodes whose table segment was rewritten and whose plane rows were not yet: kept until the plane refresh consumed them
+    bool fx_pending_whole = false;  // ... the table was derived whole since
+    int64_t fx_derived = 0, fx_patches = 0;
   } vt;
 
   void clear_state() {
@@ -3906,7 +3918,7 @@ int32_t victim_capacity(size_t count) { return (int32_t)(count + count / 2 + 4);
 // Brings the mirror's victim table up to date — the dictionaries are current: the caller has synced or encoded — and, with a device, the
 // engine's copy: the segments of the marked nodes are patched; the whole table is derived when there is none, the dimensions or the
 // dictionaries moved, or a segment outgrew its capacity.
-int victims_refresh(ykhost* h) {
+int victims_refresh_table(ykhost* h) {
   ykhost::VictimMirror& v = h->vt;
   const size_t T = h->rc_bounds.size(), R = (size_t)h->enc.R, KP = (size_t)h->enc.KP, N = h->nodes.size();
   bool whole = !v.built || v.T != T || v.R != R || v.KP != KP || v.N != N;
@@ -3927,9 +3939,11 @@ int victims_refresh(ykhost* h) {
       const size_t b = (size_t)v.base[(size_t)n];
       victim_segment(h, *h->nodes[(size_t)n], order, N, v.tier_end.data() + n, v.P, v.cum.data() + b, KP ? v.ports.data() + b : nullptr);
       v.to_push.push_back(n);
+      if (v.fx_on) v.fx_pending.push_back(n);
       v.patches++;
     }
   }
+  if (whole) v.fx_pending_whole = true;
   if (whole) {
     v.built = v.on_device = false;
     v.dirty.clear();
@@ -3970,6 +3984,7 @@ int victims_refresh(ykhost* h) {
     vt.tier_end = v.tier_end.data();
     vt.cum = v.cum.data();
     vt.ports_after = KP ? v.ports.data() : nullptr;
+    v.fx_on_device = false;  // (the engine drops the effects plane with the table it described)
     const int rc = ykpred_set_victims(h->eng, &vt);
     if (rc) return fail(h, std::string("ykpred_set_victims: ") + ykpred_last_error(h->eng), rc);
     v.on_device = true;
@@ -4000,6 +4015,110 @@ int victims_refresh(ykhost* h) {
     }
   }
   return 0;
+}
+// One node's rows of the effects plane: per victim i of the order the PREFIX sum of its contributions to the classes that have a column,
+// at cum[col * pstride + i]. false: a victim contributes to a class without a column (the plane must be derived anew).
+bool victim_effects_segment(ykhost* h, const std::vector<const Pod*>& order, const std::vector<int32_t>& class_col, size_t pstride, int32_t* cum) {
+  const size_t KS = class_col.size();
+  std::vector<int32_t> sum(KS, 0);
+  for (size_t i = 0; i < order.size(); ++i) {
+    for (size_t s = 0; s < KS; ++s) {
+      const int c = h->enc.pod_class_contribution((int)s, *order[i]);
+      if (c != 0 && class_col[s] < 0) return false;
+      sum[s] += c;
+    }
+    for (size_t s = 0; s < KS; ++s)
+      if (class_col[s] >= 0) cum[(size_t)class_col[s] * pstride + i] = sum[s];
+  }
+  return true;
+}
+// The effects plane behind the victim table the mirror now holds: fx_pending = the nodes whose segments were rewritten since the plane last
+// followed, fx_pending_whole = the table was derived whole since.
+int victim_effects_refresh(ykhost* h) {
+  ykhost::VictimMirror& v = h->vt;
+  std::vector<int> patched;
+  patched.swap(v.fx_pending);
+  std::sort(patched.begin(), patched.end());
+  patched.erase(std::unique(patched.begin(), patched.end()), patched.end());
+  const bool derived = v.fx_pending_whole;
+  v.fx_pending_whole = false;
+  const size_t KS = (size_t)h->enc.KS, N = v.N;
+  const uint64_t digest = h->enc.topology_dictionary_digest();
+  bool whole = derived || !v.fx_built || v.fx_digest != digest || v.KS != KS || v.fx_P != v.P;
+  std::vector<const Pod*> order;
+  if (!whole)
+    for (int n : patched) {
+      victim_order(h, *h->nodes[(size_t)n], &order);
+      const size_t b = (size_t)v.base[(size_t)n];
+      // (rows behind the victims are slack: never read)
+      if (!victim_effects_segment(h, order, v.class_col, v.P, v.fx_cum.data() + b)) {
+        whole = true;
+        break;
+      }
+      v.fx_to_push.push_back(n);
+      v.fx_patches++;
+    }
+  if (whole) {
+    v.fx_built = v.fx_on_device = false;
+    v.fx_to_push.clear();
+    v.KS = KS, v.fx_P = v.P, v.fx_digest = digest;
+    v.class_col.assign(KS, -1);
+    std::vector<std::vector<const Pod*>> orders(N);
+    std::vector<uint8_t> used(KS + 1, 0);
+    for (size_t n = 0; n < N; ++n) {
+      victim_order(h, *h->nodes[n], &orders[n]);
+      for (const Pod* p : orders[n])
+        for (size_t s = 0; s < KS; ++s)
+          if (!used[s] && h->enc.pod_class_contribution((int)s, *p) != 0) used[s] = 1;
+    }
+    v.KA = 0;
+    for (size_t s = 0; s < KS; ++s)
+      if (used[s]) v.class_col[s] = (int32_t)v.KA++;
+    v.fx_cum.assign(v.KA * v.P + 1, 0);
+    for (size_t n = 0; n < N; ++n) victim_effects_segment(h, orders[n], v.class_col, v.P, v.fx_cum.data() + (size_t)v.base[n]);
+    v.fx_built = true;
+    v.fx_derived++;
+  }
+  if (h->device < 0) {
+    v.fx_to_push.clear();
+    return 0;
+  }
+  if (!v.fx_on_device) {
+    ykpred_victim_effects_t fx{};
+    fx.classes = (int32_t)KS;
+    fx.columns = (int32_t)v.KA;
+    fx.rows = (int64_t)v.P;
+    fx.class_col = v.class_col.data();
+    fx.cum = v.fx_cum.data();
+    const int rc = ykpred_set_victim_effects(h->eng, &fx);
+    if (rc) return fail(h, std::string("ykpred_set_victim_effects: ") + ykpred_last_error(h->eng), rc);
+    v.fx_on_device = true;
+    v.fx_to_push.clear();
+    return 0;
+  }
+  std::vector<int> push;
+  push.swap(v.fx_to_push);
+  std::vector<int32_t> cum;
+  for (int n : push) {
+    const size_t b = (size_t)v.base[(size_t)n], count = v.T ? (size_t)v.tier_end[(v.T - 1) * N + (size_t)n] : 0;
+    cum.assign(v.KA * count + 1, 0);
+    for (size_t k = 0; k < v.KA; ++k) std::copy_n(v.fx_cum.data() + k * v.P + b, count, cum.data() + k * count);
+    const int rc = ykpred_update_victim_effects_node(h->eng, n, (int32_t)count, cum.data());
+    if (rc) {
+      v.fx_on_device = false;  // (the next call uploads the whole plane)
+      return fail(h, std::string("ykpred_update_victim_effects_node: ") + ykpred_last_error(h->eng), rc);
+    }
+  }
+  return 0;
+}
+// the victim table, and — once a live round has asked for it — its effects plane in step with it
+int victims_refresh(ykhost* h) {
+  // (the table's mirror side first, then the plane's mirror side, and only then the device: a failed push loses no patch — the nodes a
+  // failed refresh rewrote stay in fx_pending for the next one)
+  const int rc = victims_refresh_table(h);
+  if (!h->vt.fx_on || !h->vt.built) return rc;
+  const int rc2 = victim_effects_refresh(h);
+  return rc ? rc : rc2;
 }
 // sync, the reclaim table (the engine wants it beside the victim table), then the victim table
 int victims_sync(ykhost* h, const char* name) {
@@ -4172,17 +4291,34 @@ int32_t ykhost_victim_range(ykhost_t* h, int32_t node, int32_t from, int32_t cou
   return 0;
 }
 
-int32_t ykhost_preempt_round(ykhost_t* h, int32_t n, const int32_t* asks, int64_t* out_cells, int64_t* out_summary) {
-  YKHOST_LOCKED(h);
+namespace {
+// what the live round adds to the arguments: the readback of the round-local histograms
+struct LiveReadback {
+  int32_t* counts;
+  int64_t counts_len;
+  int32_t* minima;
+  int64_t minima_len;
+  int64_t* needed2;
+};
+int preempt_round_common(ykhost* h, const LiveReadback* live, int32_t n, const int32_t* asks, int64_t* out_cells, int64_t* out_summary) {
   constexpr size_t B = YKPRED_PREEMPT_ROUND_CELLS;
-  if (n < 0 || !out_summary || (n > 0 && !out_cells)) return fail(h, "preempt_round: bad argument", -1);
-  int rc = victims_sync(h, "preempt_round");
+  const char* name = live ? "preempt_round_live" : "preempt_round";
+  if (n < 0 || !out_summary || (n > 0 && !out_cells)) return fail(h, std::string(name) + ": bad argument", -1);
+  if (live && (live->counts_len < 0 || live->minima_len < 0)) return fail(h, std::string(name) + ": bad argument", -1);
+  if (live && live->needed2) live->needed2[0] = live->needed2[1] = 0;
+  if (live && h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
+  if (live) h->vt.fx_on = true;  // (from here on the mirror keeps the effects plane beside the victim table)
+  int rc = victims_sync(h, name);
   if (rc) return rc;
+  if (live) {
+    rc = upload_spec_effects(h, true);
+    if (rc) return rc;
+  }
   int32_t world = 1;
   ykpred_comm_info(h->eng, nullptr, &world, nullptr);
   const int P = (int)h->pending.size();
   for (int i = 0; i < n; ++i)
-    if ((asks ? asks[i] : i) < 0 || (asks ? asks[i] : i) >= P) return fail(h, "preempt_round: ask index out of range", YKPRED_E_INVALID);
+    if ((asks ? asks[i] : i) < 0 || (asks ? asks[i] : i) >= P) return fail(h, std::string(name) + ": ask index out of range", YKPRED_E_INVALID);
   // (an ask routed to the CPU manager is settled here and changes nothing; on a node-sharded handle every ask goes to the engine)
   std::vector<int32_t> list, limits, slot;
   int64_t routed = 0;
@@ -4203,10 +4339,59 @@ int32_t ykhost_preempt_round(ykhost_t* h, int32_t n, const int32_t* asks, int64_
     }
   }
   std::vector<int64_t> rows(list.size() * B + 1);
-  rc = ykpred_preempt_round(h->eng, (int32_t)list.size(), list.data(), limits.data(), h->alloc_pre, h->alloc_filt, rows.data(), out_summary);
-  if (rc) return fail(h, std::string("ykpred_preempt_round: ") + ykpred_last_error(h->eng), rc);
+  if (!live) {
+    rc = ykpred_preempt_round(h->eng, (int32_t)list.size(), list.data(), limits.data(), h->alloc_pre, h->alloc_filt, rows.data(), out_summary);
+    if (rc) return fail(h, std::string("ykpred_preempt_round: ") + ykpred_last_error(h->eng), rc);
+  } else {
+    int64_t dims[2] = {0, 0};
+    rc = ykpred_histogram_dims(h->eng, dims);
+    if (rc) return fail(h, std::string("ykpred_histogram_dims: ") + ykpred_last_error(h->eng), rc);
+    std::vector<int32_t> counts((size_t)dims[0] + 1, 0), minima((size_t)dims[1] + 1, 0);
+    rc = ykpred_preempt_round_live(h->eng, (int32_t)list.size(), list.data(), limits.data(), h->alloc_pre, h->alloc_filt, rows.data(), out_summary,
+                                   counts.data(), minima.data());
+    if (rc) return fail(h, std::string("ykpred_preempt_round_live: ") + ykpred_last_error(h->eng), rc);
+    if (live->counts) std::copy_n(counts.begin(), (size_t)std::min<int64_t>(dims[0], live->counts_len), live->counts);
+    if (live->minima) std::copy_n(minima.begin(), (size_t)std::min<int64_t>(dims[1], live->minima_len), live->minima);
+    if (live->needed2) live->needed2[0] = dims[0], live->needed2[1] = dims[1];
+  }
   out_summary[3] += routed;
   for (size_t k = 0; k < list.size(); ++k) memcpy(out_cells + (size_t)slot[k] * B, rows.data() + k * B, B * sizeof(int64_t));
+  return 0;
+}
+}  // namespace
+
+int32_t ykhost_preempt_round(ykhost_t* h, int32_t n, const int32_t* asks, int64_t* out_cells, int64_t* out_summary) {
+  YKHOST_LOCKED(h);
+  return preempt_round_common(h, nullptr, n, asks, out_cells, out_summary);
+}
+
+int32_t ykhost_preempt_round_live(ykhost_t* h, int32_t n, const int32_t* asks, int64_t* out_cells, int64_t* out_summary, int32_t* out_counts,
+                                  int64_t counts_len, int32_t* out_minima, int64_t minima_len, int64_t* hist_needed2) {
+  YKHOST_LOCKED(h);
+  const LiveReadback live{out_counts, counts_len, out_minima, minima_len, hist_needed2};
+  return preempt_round_common(h, &live, n, asks, out_cells, out_summary);
+}
+
+int32_t ykhost_victim_effects(ykhost_t* h, int32_t* dims, int32_t* class_col, int32_t* cum) {
+  YKHOST_LOCKED(h);
+  if (!dims) return fail(h, "victim_effects: bad argument", -1);
+  if (h->rc_bounds.empty()) return fail(h, "victim_effects: no preemption tiers (ykhost_set_preemption_tiers)", YKPRED_E_STATE);
+  h->vt.fx_on = true;
+  int rc = 0;
+  if (h->device < 0) {  // (a mirror-only handle encodes for the dictionaries alone, as ykhost_victim_table does)
+    EncodedTables T;
+    rc = encode_tables(h, &T);
+    h->dirty_all = true;
+    if (!rc) rc = victims_refresh(h);
+  } else {
+    rc = victims_sync(h, "victim_effects");
+  }
+  if (rc) return rc;
+  const ykhost::VictimMirror& v = h->vt;
+  dims[0] = (int32_t)v.KS, dims[1] = (int32_t)v.KA, dims[2] = (int32_t)v.P, dims[3] = (int32_t)v.fx_derived, dims[4] = (int32_t)v.fx_patches;
+  if (!class_col || !cum) return 0;
+  std::copy_n(v.class_col.begin(), v.KS, class_col);
+  std::copy_n(v.fx_cum.begin(), v.KA * v.P, cum);
   return 0;
 }
 
@@ -4221,10 +4406,11 @@ int round_row_by_key(ykhost* h, const char* allocation_key, const Pod** pod) {
   return 0;
 }
 // The round over ask rows, then per ask the node by name and the uids order(node)[from .. from + extra).
-int round_names_and_uids(ykhost* h, int32_t n, const int32_t* rows, int64_t* out_cells, int64_t* out_summary, char* node_names, int64_t names_len,
-                         char* victim_uids_buf, int64_t uids_len, int64_t* needed2) {
+int round_names_and_uids(ykhost* h, bool live, int32_t n, const int32_t* rows, int64_t* out_cells, int64_t* out_summary, char* node_names,
+                         int64_t names_len, char* victim_uids_buf, int64_t uids_len, int64_t* needed2) {
   constexpr size_t B = YKPRED_PREEMPT_ROUND_CELLS;
-  int rc = ykhost_preempt_round(h, n, rows, out_cells, out_summary);
+  const LiveReadback no_readback{nullptr, 0, nullptr, 0, nullptr};
+  int rc = preempt_round_common(h, live ? &no_readback : nullptr, n, rows, out_cells, out_summary);
   if (rc) return rc;
   int32_t offset = 0;
   ykpred_comm_info(h->eng, nullptr, nullptr, &offset);
@@ -4244,11 +4430,11 @@ int round_names_and_uids(ykhost* h, int32_t n, const int32_t* rows, int64_t* out
 }  // namespace
 
 // The list named as the core names it, one crossing: the cells, and per ask the node by name and its victims by uid.
-int32_t ykhost_preempt_round_by_keys(ykhost_t* h, int32_t n, const char* const* allocation_keys, int64_t* out_cells, int64_t* out_summary,
-                                     char* node_names, int64_t names_len, char* victim_uids_buf, int64_t uids_len, int64_t* needed2) {
-  YKHOST_LOCKED(h);
+namespace {
+int round_by_keys(ykhost* h, bool live, int32_t n, const char* const* allocation_keys, int64_t* out_cells, int64_t* out_summary, char* node_names,
+                  int64_t names_len, char* victim_uids_buf, int64_t uids_len, int64_t* needed2) {
   if (n < 0 || !out_summary || (n > 0 && (!allocation_keys || !out_cells)) || names_len < 0 || uids_len < 0)
-    return fail(h, "preempt_round_by_keys: bad argument", -1);
+    return fail(h, live ? "preempt_round_live_by_keys: bad argument" : "preempt_round_by_keys: bad argument", -1);
   if (needed2) needed2[0] = needed2[1] = 0;
   if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
   ensure_uid_index(h);
@@ -4259,13 +4445,12 @@ int32_t ykhost_preempt_round_by_keys(ykhost_t* h, int32_t n, const char* const* 
   if (rc) return rc;
   std::vector<int32_t> rows((size_t)n + 1);
   for (int i = 0; i < n; ++i) rows[(size_t)i] = pods[(size_t)i]->row;
-  return round_names_and_uids(h, n, rows.data(), out_cells, out_summary, node_names, names_len, victim_uids_buf, uids_len, needed2);
+  return round_names_and_uids(h, live, n, rows.data(), out_cells, out_summary, node_names, names_len, victim_uids_buf, uids_len, needed2);
 }
 
-int32_t ykhost_preempt_gang_by_key(ykhost_t* h, const char* allocation_key, int32_t want, int64_t* out_cells, int64_t* out_summary, char* node_names,
-                                   int64_t names_len, char* victim_uids_buf, int64_t uids_len, int64_t* needed2) {
-  YKHOST_LOCKED(h);
-  if (want < 0 || !out_summary || (want > 0 && !out_cells) || names_len < 0 || uids_len < 0) return fail(h, "preempt_gang_by_key: bad argument", -1);
+int gang_by_key(ykhost* h, bool live, const char* allocation_key, int32_t want, int64_t* out_cells, int64_t* out_summary, char* node_names,
+                int64_t names_len, char* victim_uids_buf, int64_t uids_len, int64_t* needed2) {
+  if (want < 0 || !out_summary || (want > 0 && !out_cells) || names_len < 0 || uids_len < 0) return fail(h, live ? "preempt_gang_live_by_key: bad argument" : "preempt_gang_by_key: bad argument", -1);
   if (needed2) needed2[0] = needed2[1] = 0;
   if (h->device < 0) return fail(h, "mirror-only handle (device < 0): no device engine, nothing can be evaluated", YKPRED_E_STATE);
   ensure_uid_index(h);
@@ -4275,7 +4460,29 @@ int32_t ykhost_preempt_gang_by_key(ykhost_t* h, const char* allocation_key, int3
   rc = sync(h);
   if (rc) return rc;
   std::vector<int32_t> rows((size_t)want + 1, pod->row);
-  return round_names_and_uids(h, want, rows.data(), out_cells, out_summary, node_names, names_len, victim_uids_buf, uids_len, needed2);
+  return round_names_and_uids(h, live, want, rows.data(), out_cells, out_summary, node_names, names_len, victim_uids_buf, uids_len, needed2);
+}
+}  // namespace
+
+int32_t ykhost_preempt_round_by_keys(ykhost_t* h, int32_t n, const char* const* allocation_keys, int64_t* out_cells, int64_t* out_summary,
+                                     char* node_names, int64_t names_len, char* victim_uids_buf, int64_t uids_len, int64_t* needed2) {
+  YKHOST_LOCKED(h);
+  return round_by_keys(h, false, n, allocation_keys, out_cells, out_summary, node_names, names_len, victim_uids_buf, uids_len, needed2);
+}
+int32_t ykhost_preempt_gang_by_key(ykhost_t* h, const char* allocation_key, int32_t want, int64_t* out_cells, int64_t* out_summary, char* node_names,
+                                   int64_t names_len, char* victim_uids_buf, int64_t uids_len, int64_t* needed2) {
+  YKHOST_LOCKED(h);
+  return gang_by_key(h, false, allocation_key, want, out_cells, out_summary, node_names, names_len, victim_uids_buf, uids_len, needed2);
+}
+int32_t ykhost_preempt_round_live_by_keys(ykhost_t* h, int32_t n, const char* const* allocation_keys, int64_t* out_cells, int64_t* out_summary,
+                                          char* node_names, int64_t names_len, char* victim_uids_buf, int64_t uids_len, int64_t* needed2) {
+  YKHOST_LOCKED(h);
+  return round_by_keys(h, true, n, allocation_keys, out_cells, out_summary, node_names, names_len, victim_uids_buf, uids_len, needed2);
+}
+int32_t ykhost_preempt_gang_live_by_key(ykhost_t* h, const char* allocation_key, int32_t want, int64_t* out_cells, int64_t* out_summary,
+                                        char* node_names, int64_t names_len, char* victim_uids_buf, int64_t uids_len, int64_t* needed2) {
+  YKHOST_LOCKED(h);
+  return gang_by_key(h, true, allocation_key, want, out_cells, out_summary, node_names, names_len, victim_uids_buf, uids_len, needed2);
 }
 
 // ---- headroom per topology domain (ykpred_headroom_groups) --------------------------------------------------------------------------

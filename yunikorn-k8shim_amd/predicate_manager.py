@@ -956,6 +956,73 @@ class GpuPredicateManager:
             self._pcheck(self._P.ykpred_preempt_round(self.engine, count, ptr, limits.ctypes.data, pre, filt, out.ctypes.data, summary.ctypes.data))
         return out[:count].copy(), summary
 
+    # ---- preemption round with live topology histograms: coupled asks take their turn ----------------------------------------
+    def preempt_round_live(self, pods=None, pre_mask=None, filt_mask=None, histograms=False):
+        """preempt_round for lists that hold asks with a hard topology spread or required pod (anti-)affinity
+        (ykpred_preempt_round_live): no ask is settled as coupled, every ask takes its turn against the topology histograms as the
+        earlier placements and the earlier victims left them → (cells, summary) as preempt_round, summary[7] = (turn, constraint)
+        pairs that moved a histogram cell; with histograms=True also (np.int32[layout().spread_cells] counts, np.int32[G] minima): the
+        round-local histograms after the last turn. Nothing in the mirror or on the device changes. Explicit masks go to the engine
+        with the limits the host derives."""
+        if pods is None:
+            count, ptr = self.num_pods, None
+        else:
+            idx = [p if isinstance(p, (int, np.integer)) else self.pod_index(p) for p in pods]
+            arr = np.ascontiguousarray(idx, dtype=np.int32)
+            count, ptr = len(arr), arr.ctypes.data
+        out = np.zeros((max(count, 1), PREEMPT_ROUND_CELLS), dtype=np.int64)
+        summary = np.zeros(8, dtype=np.int64)
+        dims = np.zeros(2, dtype=np.int64)
+        counts, minima = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+        if pre_mask is None and filt_mask is None:
+            for _ in range(2):   # (the sizes come back with the first answer; the round starts from the same state each call)
+                self._check(self._L.ykhost_preempt_round_live(self._h, count, ptr, out.ctypes.data, summary.ctypes.data, counts.ctypes.data, len(counts),
+                                                              minima.ctypes.data, len(minima), dims.ctypes.data))
+                if not histograms or (dims[0] <= len(counts) and dims[1] <= len(minima)):
+                    break
+                counts, minima = np.zeros(max(int(dims[0]), 1), dtype=np.int32), np.zeros(max(int(dims[1]), 1), dtype=np.int32)
+        else:
+            pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
+            self.victim_effects(planes=False)   # (syncs the tables, the reclaim table, the victim table and its effects plane)
+            self._check(self._L.ykhost_preempt_round_live(self._h, 0, None, out.ctypes.data, summary.ctypes.data, None, 0, None, 0, dims.ctypes.data))
+            limits = np.zeros(max(count, 1), dtype=np.int32)
+            self._check(self._L.ykhost_preempt_limits(self._h, count, ptr, limits.ctypes.data))
+            if ptr is None:
+                arr = np.arange(count, dtype=np.int32)
+                ptr = arr.ctypes.data
+            self._pcheck(self._P.ykpred_histogram_dims(self.engine, dims.ctypes.data))
+            counts, minima = np.zeros(max(int(dims[0]), 1), dtype=np.int32), np.zeros(max(int(dims[1]), 1), dtype=np.int32)
+            self._pcheck(self._P.ykpred_preempt_round_live(self.engine, count, ptr, limits.ctypes.data, pre, filt, out.ctypes.data, summary.ctypes.data,
+                                                           counts.ctypes.data, minima.ctypes.data))
+        if histograms:
+            return out[:count].copy(), summary, counts[:int(dims[0])].copy(), minima[:int(dims[1])].copy()
+        return out[:count].copy(), summary
+
+    def preempt_round_live_by_keys(self, uids):
+        """preempt_round_by_keys over the live round, ONE crossing (ykhost_preempt_round_live_by_keys)."""
+        keys = [u.encode() for u in uids]
+        arr = (C.c_char_p * max(len(keys), 1))(*keys)
+        return self._round_by_keys(lambda *a: self._L.ykhost_preempt_round_live_by_keys(self._h, len(keys), C.addressof(arr), *a), len(keys))
+
+    def preempt_gang_live(self, uid, want):
+        """`want` copies of one ask — a gang with a zone spread, a "one per host" rule, workers beside their driver — as a live round
+        (ykhost_preempt_gang_live_by_key) → as preempt_round_by_keys."""
+        return self._round_by_keys(lambda *a: self._L.ykhost_preempt_gang_live_by_key(self._h, uid.encode(), int(want), *a), int(want))
+
+    def victim_effects(self, planes=True):
+        """The victim-effects plane as the mirror keeps it (ykhost_victim_effects; works without a device) → dict(class_col
+        np.int32[KS] — the column of a selector class or -1 —, cum np.int32[KA, P] — prefix sums of the victims' contributions within
+        each segment of victim_table() —, derived, patches)."""
+        dims = np.zeros(5, dtype=np.int32)
+        self._check(self._L.ykhost_victim_effects(self._h, dims.ctypes.data, None, None))
+        if not planes:
+            return None
+        KS, KA, P = (int(x) for x in dims[:3])
+        col, cum = np.zeros(KS, dtype=np.int32), np.zeros((KA, P), dtype=np.int32)
+        pad = [np.zeros(1, dtype=np.int32) if a.size == 0 else a for a in (col, cum)]
+        self._check(self._L.ykhost_victim_effects(self._h, dims.ctypes.data, *(a.ctypes.data for a in pad)))
+        return dict(class_col=col, cum=cum, derived=int(dims[3]), patches=int(dims[4]))
+
     def _round_by_keys(self, call, count):
         names_len, uids_len = 64 * count + 256, 64 * count + (1 << 12)
         while True:
