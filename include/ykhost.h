@@ -352,6 +352,35 @@ int32_t ykhost_reclaim_table(ykhost_t* h, int32_t* dims /* [4] */, int64_t* requ
  * ykhost_preempt_reach and without an engine query: what a caller of ykpred_preempt_reach with plugin lists of its own passes on. */
 int32_t ykhost_preempt_limits(ykhost_t* h, int32_t n, const int32_t* asks /* NULL = asks 0..n-1 */, int32_t* out_limits /* [n] */);
 
+/* PREEMPTION EXPLAIN (ykpred.h: ykpred_preempt_explain) — WHY an ask is still pending with preemption on: the second sentence of
+ * kube-scheduler's message for an unschedulable pod, "preemption: 0/5000 nodes are available: 3000 Preemption is not helpful for
+ * scheduling, 1500 No preemption victims found for incoming pod, 500 Insufficient memory.", behind ykhost_explain's first one. The tiers
+ * are those of ykhost_set_preemption_tiers, the limits are derived and the reclaim table is kept up to date exactly as for
+ * ykhost_preempt_reach; always the ALLOCATION-phase plugin lists.
+ *   ykhost_preempt_explain          syncs and makes ONE engine call for the listed asks (NULL = asks 0..n-1): out_cells[i] = the
+ *                                   YKPRED_PREEMPT_EXPLAIN_CELLS cells. An ask routed to the CPU manager gets [10] = N and status [30] = 1
+ *                                   without a device call. YKPRED_E_STATE without tiers. Collective on a node-sharded handle: every rank
+ *                                   passes the same asks.
+ *   ykhost_preempt_explain_nodes    the per-node word of ONE ask on every node (ykpred_preempt_explain_pod); this shard's nodes on a
+ *                                   node-sharded handle.
+ *   ykhost_preempt_explain_format   a PURE function of the cells and the handle's resource names (works on a mirror-only handle):
+ *                                   total = cells[0] + ... + cells[11]; "preemption: <cells[11]>/<total> nodes are available" + the
+ *                                   entries in ykhost_explain_format's style (counts > 0 only, equal texts merged, the entry strings
+ *                                   sorted bytewise; "0/0 nodes are available." for an empty total): [25] "Preemption is not helpful
+ *                                   for scheduling", [24] "No preemption victims found for incoming pod", [27] the NodePorts text and
+ *                                   [12] the too-many-pods text of the per-pair messages, [16 + r] "Insufficient <resource r>", [10]
+ *                                   the routed-ask text of ykhost_explain_format. A not-enough node whose last failure is a frozen
+ *                                   plugin behind NodeResourcesFit is in [26] and has no entry. The wording is kube-scheduler's
+ *                                   PostFilter message of the default preemption plugin (upstream wording, not reference-held).
+ *                                   → required length incl. NUL; writes at most `len` bytes.
+ *   ykhost_preempt_explain_message  ONE crossing for one ask by allocation key (pod UID): ykhost_explain_format's sentence of the
+ *                                   allocation phase, a space, then the preemption sentence — as kube-scheduler joins them. → required
+ *                                   length, or the errors of ykhost_explain_message. */
+int32_t ykhost_preempt_explain(ykhost_t* h, int32_t n, const int32_t* asks /* NULL = asks 0..n-1 */, int64_t* out_cells /* [n][32] */);
+int32_t ykhost_preempt_explain_nodes(ykhost_t* h, int32_t pod, uint32_t* out /* [N] */);
+int64_t ykhost_preempt_explain_format(ykhost_t* h, const int64_t* cells /* [32] */, char* out, int64_t len);
+int64_t ykhost_preempt_explain_message(ykhost_t* h, const char* allocation_key, char* out, int64_t len);
+
 /* PREEMPTION HEADROOM (ykpred.h: ykpred_preempt_headroom) — can preemption up to the ask's priority place the whole gang, at which level,
  * and at the cost of how many resident pods? — asked where a task group creates its minMember placeholders, before the timeout wait.
  * The tiers are those of ykhost_set_preemption_tiers, the limits are derived and the reclaim table is kept up to date exactly as for

@@ -38,7 +38,9 @@
 extern "C" {
 #endif
 
-/* (ykpred_preempt_round_live + ykpred_histogram_dims + ykpred_set_victim_effects + ykpred_update_victim_effects_node + ykpred_victim_effects_t arrived WITHIN
+/* (ykpred_preempt_explain + ykpred_preempt_explain_pod + YKPRED_PREEMPT_EXPLAIN_CELLS arrived WITHIN version 4 too:
+ *    dlsym("ykpred_preempt_explain"))
+ * (ykpred_preempt_round_live + ykpred_histogram_dims + ykpred_set_victim_effects + ykpred_update_victim_effects_node + ykpred_victim_effects_t arrived WITHIN
  *    version 4 too: dlsym("ykpred_preempt_round_live"))
  * (ykpred_preempt_round + YKPRED_PREEMPT_ROUND_CELLS arrived WITHIN version 4 too: dlsym("ykpred_preempt_round"))
  * (ykpred_preempt_victims + ykpred_preempt_victims_pod + ykpred_set_victims + ykpred_update_victims_node + YKPRED_VICTIM_CELLS arrived
@@ -737,6 +739,55 @@ int32_t ykpred_preempt_reach(ykpred_engine_t* e, int32_t n_asks, const int32_t* 
  * the real victim selection. -1 everywhere for a YKPRED_SPEC_UNSUPPORTED spec. This shard's nodes only on a sharded engine. */
 int32_t ykpred_preempt_reach_pod(ykpred_engine_t* e, int32_t pod_index, int32_t limit, uint32_t prefilter_plugins, uint32_t filter_plugins,
                                  int32_t* out /* [N] */);
+
+/* PREEMPTION EXPLAIN — WHY removing lower-priority pods opens no node: ykpred_explain's histogram on the node states of
+ * ykpred_preempt_reach, what kube-scheduler prints as "preemption: 0/5000 nodes are available: 3000 Preemption is not helpful for
+ * scheduling, 1500 No preemption victims found for incoming pod, 500 Insufficient memory." 
+ *
+ * For an ask a with limit l and a node n (limits and tiers exactly those of ykpred_preempt_reach): level(a, n) is the reach level;
+ * elig(n, l) = the node's pods in tiers < l; final(n, l) = the node with ALL pods of tiers < l gone, removed as ykpred_preempt_reach
+ * removes them (free resources grow by the tier requests, len(Pods) drops, the port words become ports_after of the last non-empty
+ * tier, the topology PreFilter state stays frozen); V(a, n) = the (code, reason) of Predicates(a, final(n, l)). Only NEVER nodes are
+ * classified, each into exactly one class:
+ *   UNRESOLVABLE  the first failing code as the node stands is neither NodePorts (5) nor NodeResourcesFit (6): no removal moves it, and
+ *                 V is the verdict as the node stands
+ *   NO VICTIMS    the code is 5 or 6 and elig == 0
+ *   NOT ENOUGH    the code is 5 or 6 and elig > 0: every eligible pod is gone and the ask still fails */
+#define YKPRED_PREEMPT_EXPLAIN_CELLS 32
+/* per ask, int64[32], over all nodes of the table:
+ *  [0..8]   NEVER nodes whose FIRST failing plugin code in V is 0..8
+ *  [9]      nodes at level 0 (== cell [0] of ykpred_preempt_reach, bin [9] of ykpred_explain)
+ *  [10]     nodes not evaluated because the ask's spec is YKPRED_SPEC_UNSUPPORTED (then [10] == N and every other count cell is 0)
+ *  [11]     nodes at a level 1..limit: the nodes preemption opens (== the sum of cells [1..8] of ykpred_preempt_reach)
+ *  [12..15] NOT ENOUGH nodes whose V carries reason bit 0..3
+ *  [16..23] NOT ENOUGH nodes whose V carries "insufficient resource r", r = 0..7
+ *  [24]     NO VICTIMS nodes
+ *  [25]     UNRESOLVABLE nodes
+ *  [26]     NOT ENOUGH nodes
+ *  [27]     NOT ENOUGH nodes whose first failure in V is NodePorts (the held triple belongs to a pod in no eligible tier)
+ *  [28]     the sum of elig over the NOT ENOUGH nodes: pods whose eviction would be wasted
+ *  [29]     the limit, echoed
+ *  [30]     status: 0 computed; 1 the ask's spec is YKPRED_SPEC_UNSUPPORTED
+ *  [31]     0
+ * Invariants at status 0: [0] + ... + [11] == N; [0] + ... + [8] == [24] + [25] + [26] == cell [9] of ykpred_preempt_reach;
+ *   [27] <= [26]; a node with several reason bits counts in each of their bins. At limit 0: [26] == [27] == [28] == 0, [12..23] == 0,
+ *   [0..9] are ykpred_explain's bins, [24] == its [5] + [6] and [25] == its [0..4] + [7] + [8].
+ * Source of the verdicts: the kernel (k_preempt_explain) calls the per-pair routine of ykpred_query on the states of
+ *   ykpred_preempt_reach's tier walk; no plugin rule and no removal rule is stated a second time.
+ * Everything else is ykpred_preempt_reach's: the listed asks are reduced to their distinct (spec, NodeName, limit) tasks; the call reads
+ *   the TABLES only, needs no evaluation and invalidates none; it prepares the topology histograms as ykpred_query does; it counts as
+ *   one query; roctx range "ykpred:preempt_explain"; the same errors (YKPRED_E_STATE without a reclaim table, YKPRED_E_INVALID for a
+ *   limit outside 0..T).
+ * NODE-SHARDED engines: COLLECTIVE like ykpred_preempt_reach — the agreement all-gather first (it covers the limits), then ONE
+ *   all-reduce SUM (int64) of the cells: every rank returns CLUSTER-WIDE cells. */
+int32_t ykpred_preempt_explain(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks /* host, ask indices, any order, repeats allowed */,
+                               const int32_t* limits /* host, [n_asks], 0..T */, uint32_t prefilter_plugins, uint32_t filter_plugins,
+                               int64_t* out /* host, [n_asks][YKPRED_PREEMPT_EXPLAIN_CELLS] */);
+/* One word per node n of the table for ONE ask (thread = node, as ykpred_preempt_reach_pod): bits 0..20 ykpred_query_pod_packed's word
+ * computed on the state the verdict comes from — the node as it stands at level 0, the state at `level` when level >= 1 (fit bit
+ * set), final(n, limit) when never —, bits 24..27 the level (15 = never), bit 28 elig > 0. This shard's nodes only on a sharded engine. */
+int32_t ykpred_preempt_explain_pod(ykpred_engine_t* e, int32_t pod_index, int32_t limit, uint32_t prefilter_plugins, uint32_t filter_plugins,
+                                   uint32_t* out /* [N] */);
 
 /* PREEMPTION HEADROOM — how many copies of an ask the cluster takes per preemption level: can preemption up to the ask's priority place
  * the whole gang, what is the lowest level at which it can, and how many resident pods would that cost?

@@ -446,6 +446,39 @@ func (m *gpuPredicateManager) ExplainUnschedulable(pod *v1.Pod, allocate bool) (
 	}
 }
 
+// ExplainPreemption answers "why is this ask still pending with preemption on" with both sentences of kube-scheduler's message —
+// "0/5000 nodes are available: 3100 Insufficient cpu, ... preemption: 0/5000 nodes are available: 3000 Preemption is not helpful for
+// scheduling, 1500 No preemption victims found for incoming pod, 500 Insufficient memory." — the second one reduced on the device over
+// the node states of the preemption tiers (ykpred_preempt_explain). ONE crossing: ykhost_preempt_explain_message looks the ask up by
+// allocation key, runs both reductions with the allocation-phase plugin lists and joins the lines. Its place in the shim is that of
+// ExplainUnschedulable, for an ask whose preemption attempt came back empty (INTEGRATION.md names the call site). ("", false) when the
+// pod is not a mirrored ask, is routed to the CPU predicate manager, no preemption tiers are set, or the engine failed: the caller
+// keeps the message it has.
+func (m *gpuPredicateManager) ExplainPreemption(pod *v1.Pod) (string, bool) {
+	if pod == nil {
+		return "", false
+	}
+	var message [4096]C.char
+	uid := C.CString(string(pod.UID))
+	rc := C.ykhost_preempt_explain_message(m.host, uid, &message[0], 4096)
+	C.free(unsafe.Pointer(uid))
+	switch {
+	case rc > 0:
+		return C.GoString(&message[0]), true
+	case rc == C.YKHOST_E_UNSUPPORTED:
+		m.Counters.RoutedUnsupported.Add(1)
+		return "", false
+	case rc == C.YKHOST_E_POD_NOT_FOUND || rc == C.YKHOST_E_NOT_AN_ASK:
+		m.Counters.RoutedNotMirrored.Add(1)
+		return "", false
+	default:
+		m.Counters.RoutedOnError.Add(1)
+		log.Log(log.ShimPredicates).Warn("GPU predicate engine error, no preemption summary for the ask",
+			zap.String("error", C.GoString(C.ykhost_last_error(m.host))))
+		return "", false
+	}
+}
+
 // Headroom answers "how many copies of this ask can the cluster still place" — the figure the gang path otherwise learns by waiting
 // out placeholderTimeoutInSeconds: total = the sum over all nodes of the copies each node takes (free columns divided by the request
 // vector, bounded by the free pod slots; ykpred_headroom reduces it on the device), nodes = how many nodes take at least one, most =

@@ -12,6 +12,10 @@ from .predicate_manager import (ALL_PLUGINS, EXPLAIN_BINS, EXPLAIN_FIT, EXPLAIN_
                                 REACH_BEST_LEVEL, REACH_BEST_NODE, REACH_BEST_PODS, REACH_CELLS, REACH_LIMIT, REACH_MAX_TIERS, REACH_NEVER, REACH_STATUS,
                                 PREEMPT_HEADROOM_CELLS, PREEMPT_HEADROOM_COPIES, PREEMPT_HEADROOM_LEVEL, PREEMPT_HEADROOM_LIMIT, PREEMPT_HEADROOM_NODES,
                                 PREEMPT_HEADROOM_STATUS, PREEMPT_HEADROOM_VICTIMS, PREEMPT_HEADROOM_WANT,
+                                PREEMPT_EXPLAIN_CELLS, PREEMPT_EXPLAIN_ELIGIBLE, PREEMPT_EXPLAIN_FIT, PREEMPT_EXPLAIN_LEVEL_NEVER, PREEMPT_EXPLAIN_LEVEL_SHIFT,
+                                PREEMPT_EXPLAIN_LIMIT, PREEMPT_EXPLAIN_NOT_ENOUGH, PREEMPT_EXPLAIN_NO_VICTIMS, PREEMPT_EXPLAIN_OPENED, PREEMPT_EXPLAIN_PORTS,
+                                PREEMPT_EXPLAIN_REASON0, PREEMPT_EXPLAIN_RESOURCE0, PREEMPT_EXPLAIN_STATUS, PREEMPT_EXPLAIN_UNRESOLVABLE,
+                                PREEMPT_EXPLAIN_UNSUPPORTED, PREEMPT_EXPLAIN_WASTED,
                                 VICTIM_BEST_LEVEL, VICTIM_BEST_NEED, VICTIM_BEST_NODE, VICTIM_CELLS, VICTIM_FIT, VICTIM_LIMIT, VICTIM_NEVER, VICTIM_OPEN,
                                 VICTIM_STATUS, VICTIM_TOTAL,
                                 PREEMPT_ROUND_CELLS, PREEMPT_ROUND_EXTRA, PREEMPT_ROUND_FROM, PREEMPT_ROUND_LEVEL, PREEMPT_ROUND_LIMIT,

@@ -162,6 +162,8 @@ def load_ykpred():
     L.ykpred_update_reclaim_node.argtypes = [C.c_void_p, C.c_int32, C.POINTER(YkpredReclaim)]
     L.ykpred_preempt_reach.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     L.ykpred_preempt_reach_pod.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.ykpred_preempt_explain.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.ykpred_preempt_explain_pod.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
     L.ykpred_set_victims.argtypes = [C.c_void_p, C.POINTER(YkpredVictims)]
     L.ykpred_update_victims_node.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(YkpredVictims)]
     L.ykpred_preempt_victims.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -266,6 +268,12 @@ def load_ykhost():
     L.ykhost_preempt_reach_nodes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     L.ykhost_preempt_reach_by_key.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_char_p, C.c_int64]
     L.ykhost_preempt_limits.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.ykhost_preempt_explain.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.ykhost_preempt_explain_nodes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    L.ykhost_preempt_explain_format.restype = C.c_int64
+    L.ykhost_preempt_explain_format.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64]
+    L.ykhost_preempt_explain_message.restype = C.c_int64
+    L.ykhost_preempt_explain_message.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int64]
     L.ykhost_reclaim_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ykhost_preempt_victims.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.ykhost_preempt_victims_nodes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]

@@ -279,8 +279,9 @@ struct ykpred_engine {
   // The one table of the per-ask reduce calls (ask_query_run): [tasks][B] cells | [tasks] side column | task specs | task pins | task
   // limits. ykpred_explain: B = YKPRED_EXPLAIN_BINS int32 counts, no side column, no limits; ykpred_headroom: YKPRED_HEADROOM_CELLS
   // int64 cells, the max replicas beside them; ykpred_preempt_reach / _victims: YKPRED_REACH_CELLS / YKPRED_VICTIM_CELLS cells, the best
-  // keys beside them, limits; ykpred_preempt_headroom: YKPRED_PREEMPT_HEADROOM_CELLS per-level deltas, limits. One buffer serves all: the
-  // engine admits one call at a time and each call ends in a synchronise.
+  // keys beside them, limits; ykpred_preempt_headroom: YKPRED_PREEMPT_HEADROOM_CELLS per-level deltas, limits; ykpred_preempt_explain:
+  // YKPRED_PREEMPT_EXPLAIN_CELLS cells, no side column, limits. One buffer serves all: the engine admits one call at a time and each
+  // call ends in a synchronise.
   DevBuf d_query;
   DevBuf d_groups;  // ykpred_headroom_groups: summaries | pair wants | pair tasks | task specs | task pins | coupled | node groups | one table chunk
   DevBuf d_domain_head;  // headroom_domains_run (ykpred_headroom_spread, _affinity): summaries | tasks | one table chunk (rows | extra cells)
@@ -4848,6 +4849,63 @@ int32_t ykpred_preempt_reach_pod(ykpred_engine_t* e, int32_t pod, int32_t limit,
                        [&](dim3 grid, int32_t spec, int32_t pin, int32_t* d_out) {
                          hipLaunchKernelGGL(ykk::k_preempt_reach_pod, grid, dim3(ykk::kBlock), 0, e->own_stream, node_table(e), spec_table(e), reclaim_table(e),
                                             spec, pin, limit, pre, filt, d_out);
+                       });
+}
+
+// Why removing lower-priority pods opens no node: ykpred_explain's histogram on the node states of ykpred_preempt_reach, reduced on the
+// device (k_preempt_explain): tasks keyed with the limit, no side column, ONE SUM of the cells.
+int32_t ykpred_preempt_explain(ykpred_engine_t* e, int32_t n_asks, const int32_t* asks, const int32_t* limits, uint32_t pre, uint32_t filt, int64_t* out) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:preempt_explain");
+  if (e) e->n_queries++;
+  static_assert(ykk::kPreemptExplainCells == YKPRED_PREEMPT_EXPLAIN_CELLS, "k_preempt_explain writes the layout of ykpred.h");
+  constexpr size_t B = YKPRED_PREEMPT_EXPLAIN_CELLS;
+  if (!e) return YKPRED_E_INVALID;
+  const bool args_ok = n_asks <= 0 || (asks && limits && out);
+  auto more_checks = [&](std::string* why) { return preempt_limit_checks("preempt_explain", no_reclaim_table(e), e->rc_tiers, n_asks, limits, why); };
+  u64 more = tune_hash({(u64)(uint32_t)e->rc_tiers});
+  if (n_asks > 0 && args_ok)
+    for (int i = 0; i < n_asks; ++i) more = tune_hash({(u64)(uint32_t)limits[i]}, more);
+  AskTasks tasks;
+  tasks.extra = args_ok && n_asks > 0 ? limits : nullptr;
+  tasks.need_fit = false;
+  tasks.other_causes = "bad argument, no reclaim table, a limit outside 0 .. tiers, tables not uploaded, an index out of range or stale topology histograms";
+  bool run = false;
+  const int32_t rc = ask_query_prepare(e, "preempt_explain", n_asks, asks, args_ok, pre, filt, more_checks, more, &tasks, &run);
+  if (!run) return rc;
+  const size_t T = tasks.spec.size();
+  std::vector<int64_t> rows;
+  TRY(ask_query_run(e, tasks, B, SideColumn::kNone, [&](dim3 grid, const int32_t* d_spec, const int32_t* d_pin, const int32_t* d_limit, int64_t* d_cells, int64_t*) {
+    hipLaunchKernelGGL(ykk::k_preempt_explain, grid, dim3(ykk::kBlock), 0, e->own_stream, node_table(e), spec_table(e), reclaim_table(e), (int)T, d_spec, d_pin,
+                       d_limit, pre, filt, (ykk::i64*)d_cells);
+  }, &rows));
+  // ([30] arrives as the number of shards whose spec table does not evaluate the spec: then every node counts as not evaluated)
+  for (size_t k = 0; k < T; ++k) {
+    int64_t* row = rows.data() + k * B;
+    if (row[30] != 0) {
+      int64_t nodes = 0;
+      for (int c = 0; c <= 11; ++c) nodes += row[c];
+      std::fill(row, row + B, (int64_t)0);
+      row[10] = nodes;
+      row[30] = 1;
+    }
+    row[29] = tasks.extra_of[k];
+  }
+  scatter_task_rows(rows, tasks, B, out);
+  return YKPRED_OK;
+}
+
+// the verdict word of one ask on every node of this table
+int32_t ykpred_preempt_explain_pod(ykpred_engine_t* e, int32_t pod, int32_t limit, uint32_t pre, uint32_t filt, uint32_t* out) {
+  YK_SERIALISE(e);
+  Range roctx_range("ykpred:preempt_explain_pod");
+  if (e) e->n_queries++;
+  PodQuery q{"preempt_explain_pod"};
+  q.no_table = no_reclaim_table, q.tiers = &ykpred_engine::rc_tiers;
+  return pod_query_run(e, q, pod, limit, pre, filt, out,
+                       [&](dim3 grid, int32_t spec, int32_t pin, uint32_t* d_out) {
+                         hipLaunchKernelGGL(ykk::k_preempt_explain_pod, grid, dim3(ykk::kBlock), 0, e->own_stream, node_table(e), spec_table(e),
+                                            reclaim_table(e), spec, pin, limit, pre, filt, d_out);
                        });
 }
 

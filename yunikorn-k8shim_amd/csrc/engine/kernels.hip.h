@@ -3836,6 +3836,136 @@ __global__ __launch_bounds__(kBlock) void k_preempt_reach_pod(NodeTable t, SpecT
   out[n] = level == kReachNever ? -1 : level;
 }
 
+// ykpred_preempt_explain: WHY removing lower-priority pods opens no node — ykpred_explain's histogram on the node states of
+// ykpred_preempt_reach. reach_verdict is reach_level's sibling: the same walk on the same working copy, but it keeps the LAST verdict
+// (*code / *reason: of the node as it stands at level 0 or when no removal moves the first failure, of the state at the level when
+// there is one, of the node with every pod of tiers < limit gone when never) and *elig, the node's pods in tiers < limit — summed over
+// every tier below the limit, also where the walk ends early or never starts. *walked: the first failure as the node stands is
+// NodePorts or NodeResourcesFit (reach_level's test), so the tiers were walked. The tier's columns come from global memory: no array
+// is indexed by the tier; the node's registers are left as they were.
+__device__ __forceinline__ int reach_verdict(const NodeTable& t, const SpecTable& s, const ReclaimTable& rc, int spec, int pin, int node,
+                                             const NodeRegs& nr, i64 count, i64 allowed, int limit, unsigned pre_mask, unsigned filt_mask,
+                                             int* code, unsigned* reason, i64* elig, bool* walked) {
+  *elig = 0;
+  const bool fits = eval_pair(s, spec, pin, node, nr, pre_mask, filt_mask, code, reason);
+  *walked = !fits && (*code == 5 || *code == 6);
+  int level = fits ? 0 : kReachNever;
+  NodeRegs w = nr;
+  i64 gone = 0;
+  for (int tier = 0; tier < limit; ++tier) {
+    const int np = rc.pods[(size_t)tier * t.n + node];
+    *elig += np;
+    if (np == 0 || !*walked || level != kReachNever) continue;  // nothing leaves: the verdict of the step before stands
+    reclaim_tier_gone(t, rc, tier, node, np, count, allowed, &w, &gone);
+    if (eval_pair(s, spec, pin, node, w, pre_mask, filt_mask, code, reason)) level = tier + 1;
+  }
+  return level;
+}
+// the word of ykpred_query_pod_packed
+__device__ __forceinline__ unsigned packed_verdict(bool ok, int code, unsigned reason) {
+  return (unsigned)(code & 0xff) | (ok ? 0x100u : 0u) | ((reason & 0xfu) << 9) | ((reason >> 8) << 13);
+}
+
+// Grid of k_explain / k_preempt_reach: blockIdx.x = chunk of kExplainTasks tasks (spec, pin, limit), blockIdx.y = 256 nodes, lane = node;
+// the node columns are loaded once per chunk. Only NEVER nodes are classified, each into one class: UNRESOLVABLE (the walk never started),
+// NO VICTIMS (walked, elig == 0), NOT ENOUGH (walked, elig > 0: every eligible pod is gone and the ask still fails). Per task the counts
+// are ballot popcounts and lane c keeps cell c of include/ykpred.h (YKPRED_PREEMPT_EXPLAIN_CELLS): [0..8] never nodes by the first
+// failing code of the last verdict, [9] level 0, [10] not evaluated, [11] a level >= 1, [12..15] / [16..23] the reason bits of the last
+// verdict over the NOT ENOUGH nodes only (skipped when the wave holds none), [24..26] the classes, [27] not enough with NodePorts last;
+// [28], Σ elig over the not-enough nodes, is a wave sum. One LDS add per wave and task; the block's waves meet in LDS; one global
+// integer add per non-zero cell. Integer adds only: the order the blocks arrive in cannot matter. [30] is the `unsupported` flag.
+constexpr int kPreemptExplainCells = 32;
+__global__ __launch_bounds__(kBlock) void k_preempt_explain(NodeTable t, SpecTable s, ReclaimTable rc, int n_tasks,
+                                                            const int* __restrict__ task_spec, const int* __restrict__ task_pin,
+                                                            const int* __restrict__ task_limit, unsigned pre_mask, unsigned filt_mask,
+                                                            i64* __restrict__ cells) {
+  __shared__ int acc[kExplainTasks * kPreemptExplainCells];
+  __shared__ u64 accelig[kExplainTasks];
+  for (int i = threadIdx.x; i < kExplainTasks * kPreemptExplainCells; i += kBlock) acc[i] = 0;
+  if (threadIdx.x < kExplainTasks) accelig[threadIdx.x] = 0;
+  __syncthreads();
+  const int lane = threadIdx.x % kWave;
+  bool live;
+  const int n = headroom_node(t, &live);
+  const int k0 = blockIdx.x * kExplainTasks, kend = min(k0 + kExplainTasks, n_tasks);
+  if (__ballot(live)) {  // (wave-uniform: a wave wholly past N skips the walk, not the barriers)
+    NodeRegs nr;
+    load_node(t, n, &nr);
+    const i64 count = live ? (i64)t.count[n] : 0, allowed = live ? (i64)t.allowed[n] : 0;
+    for (int k = k0; k < kend; ++k) {
+      int code = 0;
+      unsigned reason = 0;
+      i64 elig = 0;
+      bool walked = false;
+      const int level = live ? reach_verdict(t, s, rc, task_spec[k], task_pin[k], n, nr, count, allowed, task_limit[k], pre_mask, filt_mask, &code,
+                                             &reason, &elig, &walked)
+                             : -1;
+      const bool never = level == kReachNever && code != 255;
+      const int bin = !live ? -1 : code == 255 ? 10 : level == 0 ? 9 : level <= kReachMaxTiers ? 11 : code;
+      // 24 no victims, 25 unresolvable, 26 not enough
+      const int cls = !never ? -1 : !walked ? 25 : elig == 0 ? 24 : 26;
+      const bool short_of = cls == 26;
+      int mine = 0;
+#pragma unroll
+      for (int b = 0; b <= 11; ++b) {
+        const int c = __popcll(__ballot(bin == b));
+        if (lane == b) mine = c;
+      }
+#pragma unroll
+      for (int b = 24; b <= 26; ++b) {
+        const int c = __popcll(__ballot(cls == b));
+        if (lane == b) mine = c;
+      }
+      if (__ballot(short_of)) {  // (wave-uniform)
+        if (!short_of) reason = 0, elig = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const int c = __popcll(__ballot((reason >> b) & 1u));
+          if (lane == 12 + b) mine = c;
+        }
+#pragma unroll
+        for (int r = 0; r < kMaxR; ++r) {
+          const int c = __popcll(__ballot((reason >> (8 + r)) & 1u));
+          if (lane == 16 + r) mine = c;
+        }
+        const int c = __popcll(__ballot(short_of && code == 5));
+        if (lane == 27) mine = c;
+        u64 sum = (u64)elig;
+#pragma unroll
+        for (int off = kWave / 2; off > 0; off >>= 1) sum += (u64)__shfl_xor((unsigned long long)sum, off, kWave);
+        if (lane == 0 && sum) atomicAdd((unsigned long long*)&accelig[k - k0], (unsigned long long)sum);
+      }
+      if (lane < 28 && mine) atomicAdd(&acc[(k - k0) * kPreemptExplainCells + lane], mine);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < (kend - k0) * kPreemptExplainCells; i += kBlock) {
+    const int v = acc[i];
+    if (v) atomicAdd((u64*)&cells[(size_t)k0 * kPreemptExplainCells + i], (u64)v);
+  }
+  if ((int)threadIdx.x < kend - k0) {
+    const u64 v = accelig[threadIdx.x];
+    if (v) atomicAdd((u64*)&cells[(size_t)(k0 + threadIdx.x) * kPreemptExplainCells + 28], v);
+  }
+  headroom_unsupported(s, k0, kend, [&](int k) { return task_spec[k]; }, cells + 30, kPreemptExplainCells);
+}
+
+// the verdict word of ONE ask on every node of the table (thread = node, as k_preempt_reach_pod): bits 0..20 ykpred_query_pod_packed's
+// word on the state the verdict comes from, bits 24..27 the level (15 = never), bit 28 elig > 0
+__global__ __launch_bounds__(kBlock) void k_preempt_explain_pod(NodeTable t, SpecTable s, ReclaimTable rc, int spec, int pin, int limit,
+                                                                unsigned pre_mask, unsigned filt_mask, unsigned* __restrict__ out) {
+  int n = blockIdx.x * kBlock + threadIdx.x;
+  if (n >= t.n) return;
+  NodeRegs nr;
+  load_node(t, n, &nr);
+  int code = 0;
+  unsigned reason = 0;
+  i64 elig = 0;
+  bool walked = false;
+  const int level = reach_verdict(t, s, rc, spec, pin, n, nr, (i64)t.count[n], (i64)t.allowed[n], limit, pre_mask, filt_mask, &code, &reason, &elig, &walked);
+  out[n] = packed_verdict(level != kReachNever, code, reason) | ((level == kReachNever ? 15u : (unsigned)level) << 24) | (elig > 0 ? 1u << 28 : 0u);
+}
+
 // ykpred_preempt_headroom: copies of an ask per preemption level. rep_L(a, n) = replicas(a, n) on the node with all pods of tiers < L gone:
 // the tier walk of reach_level with replicas() in the place of eval_pair, on the same working copy. Nothing is indexed by the level in
 // registers: a lane keeps its last rep (`prev`) and the `gone` value at its last rise (`paid`); at a level where some lane of the wave

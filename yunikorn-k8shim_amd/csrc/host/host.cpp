@@ -3299,6 +3299,24 @@ int32_t ykhost_is_pod_fit_node_via_preemption(ykhost_t* h, const char* allocatio
 // vector for it. The reason texts are compose_message's, so that a summary line agrees with the per-pair messages. Out of scope: the
 // per-taint "{key: value}" breakdown of the taint entry — upstream names the first untolerated taint in each node's OWN taint order,
 // which the dictionary encoding does not keep; every taint rejection is counted under the generic text.
+// "Insufficient <resource r>" of the per-pair messages, r = 0..7, named by the handle's encoder
+std::string insufficient_text(ykhost* h, int r) {
+  static const char* base[] = {"cpu", "memory", "ephemeral-storage"};
+  if (r >= 3 && (size_t)(r - 3) >= h->enc.scalar_names.size()) {
+    // the names are the encoder's: objects that arrived since the last encode have not named their resources yet
+    if (h->device < 0) {  // (a mirror-only handle encodes without a device, like ykhost_ask_supported)
+      EncodedTables T;
+      encode_tables(h, &T);
+      h->dirty_all = true;
+    } else {
+      sync(h);
+    }
+  }
+  return std::string("Insufficient ") + (r < 3 ? std::string(base[r])
+                                         : (size_t)(r - 3) < h->enc.scalar_names.size() ? h->enc.scalar_names[(size_t)r - 3]
+                                                                                        : "resource #" + std::to_string(r));
+}
+
 std::string explain_text(ykhost* h, const int32_t* b) {
   int64_t total = 0;
   for (int i = 0; i <= 10; ++i) total += b[i];
@@ -3315,25 +3333,10 @@ std::string explain_text(ykhost* h, const int32_t* b) {
   add("node(s) didn't match Pod's node affinity/selector", (int64_t)b[4] - b[13]);
   add("node(s) didn't have free ports for the requested pod ports", b[5]);
   add("Too many pods", b[12]);
-  static const char* base[] = {"cpu", "memory", "ephemeral-storage"};
   bool fit_reasons = b[12] != 0;
   for (int r = 0; r < 8; ++r) {
     fit_reasons = fit_reasons || b[16 + r] != 0;
-    if (b[16 + r] <= 0) continue;
-    if (r >= 3 && (size_t)(r - 3) >= h->enc.scalar_names.size()) {
-      // the names are the encoder's: objects that arrived since the last encode have not named their resources yet
-      if (h->device < 0) {  // (a mirror-only handle encodes without a device, like ykhost_ask_supported)
-        EncodedTables T;
-        encode_tables(h, &T);
-        h->dirty_all = true;
-      } else {
-        sync(h);
-      }
-    }
-    add(std::string("Insufficient ") + (r < 3 ? std::string(base[r])
-                                         : (size_t)(r - 3) < h->enc.scalar_names.size() ? h->enc.scalar_names[(size_t)r - 3]
-                                                                                        : "resource #" + std::to_string(r)),
-        b[16 + r]);
+    if (b[16 + r] > 0) add(insufficient_text(h, r), b[16 + r]);
   }
   // (NodeResourcesFit's Filter without its PreFilter in the list: the only code-6 verdict without a reason)
   if (!fit_reasons) add("running \"NodeResourcesFit\" filter plugin: reading \"PreFilterNodeResourcesFit\" from cycleState: not found", b[6]);
@@ -3791,6 +3794,124 @@ int32_t ykhost_preempt_reach_by_key(ykhost_t* h, const char* allocation_key, int
   const int64_t local = out16[13] - offset;
   if (out16[13] >= 0 && local >= 0 && local < (int64_t)h->nodes.size()) copy_out(h->nodes[(size_t)local]->node.name, best_node_name, len);
   return 0;
+}
+
+// ---- preemption explain (ykpred_preempt_explain): why removing lower-priority pods opens no node -------------------------------------
+// kube-scheduler's PostFilter text over the cells of ykpred_preempt_explain: "preemption: <opened>/<total> nodes are available: <count>
+// <reason>, ..." in explain_text's style (counts > 0, equal texts merged, the "<count> <reason>" strings sorted as strings). The wording
+// is upstream's (the default preemption plugin's message, joined behind the FitError by a space); upstream wording, not reference-held:
+// the reference holds no vector for it. The NodePorts and NodeResourcesFit texts are explain_text's.
+namespace {
+std::string preempt_explain_text(ykhost* h, const int64_t* c) {
+  int64_t total = 0;
+  for (int i = 0; i <= 11; ++i) total += c[i];
+  std::map<std::string, int64_t> reasons;  // same text => one entry
+  auto add = [&](const std::string& text, int64_t count) {
+    if (count > 0) reasons[text] += count;
+  };
+  add("Preemption is not helpful for scheduling", c[25]);
+  add("No preemption victims found for incoming pod", c[24]);
+  add("node(s) didn't have free ports for the requested pod ports", c[27]);
+  add("Too many pods", c[12]);
+  for (int r = 0; r < 8; ++r)
+    if (c[16 + r] > 0) add(insufficient_text(h, r), c[16 + r]);
+  add("node(s) not evaluated: the ask is routed to the CPU predicate manager", c[10]);
+  std::vector<std::string> entries;
+  for (auto& kv : reasons) entries.push_back(std::to_string(kv.second) + " " + kv.first);
+  std::sort(entries.begin(), entries.end());
+  std::string m = "preemption: " + std::to_string(c[11]) + "/" + std::to_string(total) + " nodes are available";
+  for (size_t i = 0; i < entries.size(); ++i) m += (i ? ", " : ": ") + entries[i];
+  return m + ".";
+}
+}  // namespace
+
+int64_t ykhost_preempt_explain_format(ykhost_t* h, const int64_t* cells, char* out, int64_t len) {
+  YKHOST_LOCKED(h);
+  if (!cells) return fail(h, "preempt_explain_format: bad argument", -1);
+  const std::string m = preempt_explain_text(h, cells);
+  copy_out(m, out, len);
+  return (int64_t)m.size() + 1;
+}
+
+int32_t ykhost_preempt_explain(ykhost_t* h, int32_t n, const int32_t* asks, int64_t* out_cells) {
+  YKHOST_LOCKED(h);
+  constexpr size_t B = YKPRED_PREEMPT_EXPLAIN_CELLS;
+  if (n < 0 || (n > 0 && !out_cells)) return fail(h, "preempt_explain: bad argument", -1);
+  int rc = reclaim_sync(h, "preempt_explain");
+  if (rc) return rc;
+  int32_t world = 1;
+  ykpred_comm_info(h->eng, nullptr, &world, nullptr);
+  const int P = (int)h->pending.size();
+  for (int i = 0; i < n; ++i)
+    if ((asks ? asks[i] : i) < 0 || (asks ? asks[i] : i) >= P) return fail(h, "preempt_explain: ask index out of range", YKPRED_E_INVALID);
+  // (an ask routed to the CPU manager gets its status here; on a node-sharded handle every ask goes to the engine, as in ykhost_explain)
+  std::vector<int32_t> list, limits, slot;
+  for (int i = 0; i < n; ++i) {
+    const int row = asks ? asks[i] : i;
+    const Pod* p = h->pending[(size_t)row];
+    int64_t* c = out_cells + (size_t)i * B;
+    if (world <= 1 && h->enc.unsupported.count(p->tpl)) {
+      std::fill(c, c + B, (int64_t)0);
+      c[10] = (int64_t)h->nodes.size();
+      c[29] = reclaim_limit(h, p);
+      c[30] = 1;
+    } else {
+      list.push_back(row);
+      limits.push_back(reclaim_limit(h, p));
+      slot.push_back(i);
+    }
+  }
+  if (list.empty() && world <= 1) return 0;
+  std::vector<int64_t> rows(list.size() * B);
+  rc = ykpred_preempt_explain(h->eng, (int32_t)list.size(), list.data(), limits.data(), h->alloc_pre, h->alloc_filt, rows.data());
+  if (rc) return fail(h, std::string("ykpred_preempt_explain: ") + ykpred_last_error(h->eng), rc);
+  for (size_t k = 0; k < list.size(); ++k) memcpy(out_cells + (size_t)slot[k] * B, rows.data() + k * B, B * sizeof(int64_t));
+  return 0;
+}
+
+int32_t ykhost_preempt_explain_nodes(ykhost_t* h, int32_t pod, uint32_t* out) {
+  YKHOST_LOCKED(h);
+  if (!out) return fail(h, "preempt_explain_nodes: bad argument", -1);
+  int rc = reclaim_sync(h, "preempt_explain_nodes");
+  if (rc) return rc;
+  if (pod < 0 || pod >= (int)h->pending.size()) return fail(h, "preempt_explain_nodes: ask index out of range", YKPRED_E_INVALID);
+  rc = ykpred_preempt_explain_pod(h->eng, pod, reclaim_limit(h, h->pending[(size_t)pod]), h->alloc_pre, h->alloc_filt, out);
+  if (rc) return fail(h, std::string("ykpred_preempt_explain_pod: ") + ykpred_last_error(h->eng), rc);
+  return 0;
+}
+
+// The Message of the PodScheduled=False / Unschedulable condition with preemption on, for one ask named as the core names it: the
+// FitError sentence of the allocation phase, a space, the preemption sentence.
+int64_t ykhost_preempt_explain_message(ykhost_t* h, const char* allocation_key, char* out, int64_t len) {
+  YKHOST_LOCKED(h);
+  copy_out("", out, len);
+  ensure_uid_index(h);
+  auto it = h->by_uid.find(allocation_key ? allocation_key : "");
+  if (it == h->by_uid.end()) {
+    copy_out("predicates were not run because pod was not found in cache", out, len);  // ErrorPodNotFound (context.go:67)
+    return YKHOST_E_POD_NOT_FOUND;
+  }
+  if (!it->second->ask) {
+    copy_out("pod is cached but holds no row of the ask table (it is bound, not a pending ask)", out, len);
+    return fail(h, "pod holds no ask row", YKHOST_E_NOT_AN_ASK);
+  }
+  int rc = reclaim_sync(h, "preempt_explain_message");
+  if (rc) return rc;
+  auto un = h->enc.unsupported.find(it->second->tpl);
+  if (un != h->enc.unsupported.end()) {
+    copy_out(un->second, out, len);
+    return fail(h, "ask is not evaluated by the engine (route it to the CPU predicate manager): " + un->second, YKHOST_E_UNSUPPORTED);
+  }
+  int32_t bins[YKPRED_EXPLAIN_BINS];
+  int64_t cells[YKPRED_PREEMPT_EXPLAIN_CELLS];
+  const int32_t row = it->second->row;
+  rc = ykhost_explain(h, 1, &row, 1, bins);
+  if (rc) return rc;
+  rc = ykhost_preempt_explain(h, 1, &row, cells);
+  if (rc) return rc;
+  const std::string m = explain_text(h, bins) + " " + preempt_explain_text(h, cells);
+  copy_out(m, out, len);
+  return (int64_t)m.size() + 1;
 }
 
 // ---- preemption headroom (ykpred_preempt_headroom): copies of an ask per preemption level ------------------------------------------------

@@ -58,6 +58,17 @@ AFFINITY_HEADROOM_CELLS = 16
 # lowest level >= 1 with a node (0: none), the best node at it (fewest victim pods, lowest index; -1: none), its victim pods, 0
 REACH_CELLS, REACH_MAX_TIERS = 16, 8
 REACH_NEVER, REACH_STATUS, REACH_LIMIT, REACH_BEST_LEVEL, REACH_BEST_NODE, REACH_BEST_PODS = 9, 10, 11, 12, 13, 14
+# ykpred_preempt_explain: per ask int64[PREEMPT_EXPLAIN_CELLS] = never nodes by the first failing code of their final verdict [0..8],
+# nodes at level 0, nodes not evaluated, nodes at a level >= 1, reason bits and insufficient resources of the final verdict over the
+# not-enough nodes [12..15] / [16..23], no-victims / unresolvable / not-enough nodes, not-enough nodes held by a port, the pods whose
+# eviction would be wasted, the ask's limit, status (0 computed, 1 routed), 0. Per node (preempt_explain_nodes): query_pod_packed's word
+# | level << PREEMPT_EXPLAIN_LEVEL_SHIFT (PREEMPT_EXPLAIN_LEVEL_NEVER: never) | PREEMPT_EXPLAIN_ELIGIBLE when a pod is in a tier below
+# the limit
+PREEMPT_EXPLAIN_CELLS = 32
+(PREEMPT_EXPLAIN_FIT, PREEMPT_EXPLAIN_UNSUPPORTED, PREEMPT_EXPLAIN_OPENED, PREEMPT_EXPLAIN_REASON0, PREEMPT_EXPLAIN_RESOURCE0, PREEMPT_EXPLAIN_NO_VICTIMS,
+ PREEMPT_EXPLAIN_UNRESOLVABLE, PREEMPT_EXPLAIN_NOT_ENOUGH, PREEMPT_EXPLAIN_PORTS, PREEMPT_EXPLAIN_WASTED, PREEMPT_EXPLAIN_LIMIT,
+ PREEMPT_EXPLAIN_STATUS) = 9, 10, 11, 12, 16, 24, 25, 26, 27, 28, 29, 30
+PREEMPT_EXPLAIN_LEVEL_SHIFT, PREEMPT_EXPLAIN_LEVEL_NEVER, PREEMPT_EXPLAIN_ELIGIBLE = 24, 15, 1 << 28
 # ykpred_preempt_headroom: per ask int64[PREEMPT_HEADROOM_CELLS] = copies(L), nodes(L), victims(L) for L = 0..8 from the three row offsets,
 # status (0 computed, 1 routed, 2 coupled), the ask's limit, the want, the lowest level whose copies meet the want (-1: none), 0
 PREEMPT_HEADROOM_CELLS = 32
@@ -799,6 +810,71 @@ class GpuPredicateManager:
             raise KeyError(uid)
         self._check(rc)
         return out, buf.value.decode()
+
+    # ---- preemption explain: why removing lower-priority pods opens no node ---------------------------------------------
+    def preempt_explain(self, pods=None, pre_mask=None, filt_mask=None):
+        """Per ask WHY preemption opens no node, reduced on the device (ykpred_preempt_explain): np.int64[n, PREEMPT_EXPLAIN_CELLS] —
+        the never nodes by the first failing plugin of their verdict with every eligible pod gone, split into
+        [PREEMPT_EXPLAIN_UNRESOLVABLE] (no removal moves the failure), [PREEMPT_EXPLAIN_NO_VICTIMS] (nobody to remove) and
+        [PREEMPT_EXPLAIN_NOT_ENOUGH] (everybody removed, still failing: reason bins from [PREEMPT_EXPLAIN_REASON0] and
+        [PREEMPT_EXPLAIN_RESOURCE0]). pods: ask indices or UIDs in any order, repeats allowed; None = every ask. Always the
+        allocation-phase lists; explicit masks go to the engine with the limits the host derives. Needs no evaluation and disturbs
+        none."""
+        if pods is None:
+            count, ptr = self.num_pods, None
+        else:
+            idx = [p if isinstance(p, (int, np.integer)) else self.pod_index(p) for p in pods]
+            arr = np.ascontiguousarray(idx, dtype=np.int32)
+            count, ptr = len(arr), arr.ctypes.data
+        out = np.zeros((max(count, 1), PREEMPT_EXPLAIN_CELLS), dtype=np.int64)
+        if pre_mask is None and filt_mask is None:
+            self._check(self._L.ykhost_preempt_explain(self._h, count, ptr, out.ctypes.data))
+        else:
+            pre, filt = self._explicit_masks(True, pre_mask, filt_mask)
+            limits = np.zeros(max(count, 1), dtype=np.int32)
+            self._check(self._L.ykhost_preempt_limits(self._h, count, ptr, limits.ctypes.data))  # (syncs the tables and the reclaim table)
+            if ptr is None:
+                arr = np.arange(count, dtype=np.int32)
+                ptr = arr.ctypes.data
+            self._pcheck(self._P.ykpred_preempt_explain(self.engine, count, ptr, limits.ctypes.data, pre, filt, out.ctypes.data))
+        return out[:count].copy()
+
+    def preempt_explain_nodes(self, pod):
+        """The verdict word of ONE ask (index or UID) on every node (ykpred_preempt_explain_pod): np.uint32[N] — query_pod_packed's
+        word on the state the verdict comes from, the level from bit PREEMPT_EXPLAIN_LEVEL_SHIFT (PREEMPT_EXPLAIN_LEVEL_NEVER: never),
+        PREEMPT_EXPLAIN_ELIGIBLE when the node holds a pod below the ask's limit. On a node-sharded manager: this shard's nodes."""
+        p = pod if isinstance(pod, (int, np.integer)) else self.pod_index(pod)
+        out = np.zeros(max(self.num_nodes, 1), dtype=np.uint32)
+        self._check(self._L.ykhost_preempt_explain_nodes(self._h, int(p), out.ctypes.data))
+        return out[:self.num_nodes].copy()
+
+    def preempt_explain_format(self, cells):
+        """kube-scheduler's preemption sentence for one row of preempt_explain(): "preemption: 0/5 nodes are available: 3 Preemption is
+        not helpful for scheduling, ..." (ykhost_preempt_explain_format; a pure function of the cells and the resource names — works
+        without a device)."""
+        c = np.ascontiguousarray(cells, dtype=np.int64)
+        if c.shape != (PREEMPT_EXPLAIN_CELLS,):
+            raise ValueError(f"preempt_explain_format takes one row of {PREEMPT_EXPLAIN_CELLS} cells")
+        need = self._check(self._L.ykhost_preempt_explain_format(self._h, c.ctypes.data, None, 0))
+        buf = C.create_string_buffer(need)
+        self._check(self._L.ykhost_preempt_explain_format(self._h, c.ctypes.data, buf, need))
+        return buf.value.decode()
+
+    def preempt_explain_message(self, uid):
+        """The Message of the Unschedulable condition with preemption on, for one ask by allocation key in one crossing
+        (ykhost_preempt_explain_message): explain_format's sentence, a space, the preemption sentence. Raises UnsupportedAsk for an
+        ask routed to the CPU manager, KeyError for an unknown pod."""
+        buf = C.create_string_buffer(4096)
+        rc = self._L.ykhost_preempt_explain_message(self._h, uid.encode(), buf, 4096)
+        if rc == -13:
+            raise UnsupportedAsk(buf.value.decode())
+        if rc in (-10, -12):
+            raise KeyError(buf.value.decode())
+        self._check(rc)
+        if rc > 4096:
+            buf = C.create_string_buffer(rc)
+            self._check(self._L.ykhost_preempt_explain_message(self._h, uid.encode(), buf, rc))
+        return buf.value.decode()
 
     # ---- preemption headroom: copies of an ask per preemption level ------------------------------------------------------
     def preempt_headroom(self, pods=None, wants=None, pre_mask=None, filt_mask=None):
